@@ -6,11 +6,18 @@ C3: 3840x2160 "full quality" = the reference's v1 shading (primary visibility +
 sun march + AO + sky/clouds + glass) + the f-3 extensions reflection and rough
 normals, on the synthetic S-proc 1024x256x32 field, camera K1, the reference's
 own res/noise.bin.gz) from the HBM-resident field into an HBM-resident RGBA8
-framebuffer.  In the same N = 1 run: the v1 shading alone (config.v1),
-BASELINE configs[4] C5 (3^3-upscaled 3072x768x96 field, 16-sample soft
-shadows; config.c5) and the frame rate with the framebuffer copied to pinned
-host memory (config.fps_with_d2h, SURVEY §8d: kernel + D2H).  --config C5
-makes C5 the headline.
+framebuffer.  A plain run does what the headline figure needs: scene set-up,
+clock settle, warm-up, one timed block of exactly --steps frames, the JSON
+line.  --full adds, in the same N = 1 run: seven timed blocks (the median is
+reported), the one-stream event timing behind the roofline figures, the
+exit-table diagnostics, the v1 shading alone (config.v1), BASELINE configs[4]
+C5 (3^3-upscaled 3072x768x96 field, 16-sample soft shadows; config.c5), the
+reflect-all workload, the frame rate with the framebuffer copied to pinned
+host memory (config.fps_with_d2h, SURVEY §8d: kernel + D2H) and the CPU
+baseline; at N > 1 the render / gather split and the gathered-frame checks.
+--config C5 makes C5 the headline.  --dump-outputs DIR writes the framebuffer
+of the last timed step (float32, DIR/frame.npy; the same arguments give the
+same inputs, so two builds compare value for value).
 
 N > 1 GPUs, one process per GPU: launched by torch.distributed.run, or by
 ``python bench.py --gpus N`` itself, which starts N rank processes (fresh
@@ -80,6 +87,14 @@ def parse(argv=None):
                          "one device): every rank renders its bands on the GPU (VOXMAP_BENCH_DEVICE, default "
                          "LOCAL_RANK), the bands travel over gloo through host memory, and rank 0 checks the "
                          "gathered frame against a whole-frame vx_render (config.gather_frame_ok); not a timing")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: 7 timed blocks (median reported) instead of one, "
+                         "the one-stream event timing behind the roofline, the exit-table diagnostics, the v1 / C5 / "
+                         "reflect-all / kernel + D2H workloads, the CPU baseline, and at N > 1 the render / gather "
+                         "split and the gathered-frame checks (--no-cpu, --no-c5, --no-d2h, --cpu-seconds trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's framebuffer to DIR/frame.npy (float32; a fixed "
+                         "seeded sample of rows when the whole frame is too large, their numbers in frame_rows.npy)")
     ap.add_argument("--standin", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args(argv)
 
@@ -123,7 +138,30 @@ def spawn_ranks(n: int, argv) -> int:
 
 
 # ---------------------------------------------------------------- timing
-REPEATS = 7             # timed blocks of `steps` frames each; the line reports their median
+REPEATS = 7             # --full: timed blocks of `steps` frames each; the line reports their median
+DUMP_FRAME_BYTES = 32 << 20   # --dump-outputs: float32 bytes of frame.npy at the most
+
+
+def dump_rows(H, W):
+    """The rows of an H x W RGBA frame that --dump-outputs keeps: all of them
+    when the float32 frame fits DUMP_FRAME_BYTES, else a fixed seeded sample."""
+    import numpy as np
+    n = min(H, max(1, DUMP_FRAME_BYTES // (W * 16)))
+    if n == H:
+        return np.arange(H)
+    return np.sort(np.random.default_rng(0).choice(H, size=n, replace=False))
+
+
+def dump_outputs(path, frame_u8):
+    """DIR/frame.npy: the (rows, W, 4) float32 values of the RGBA8 framebuffer a
+    caller of the timed path receives; DIR/frame_rows.npy: which rows they are."""
+    import numpy as np
+    a = frame_u8.numpy() if hasattr(frame_u8, "numpy") else np.asarray(frame_u8)
+    H, W = a.shape[0], a.shape[1]
+    rows = dump_rows(H, W)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "frame.npy"), a[rows].astype(np.float32))
+    np.save(os.path.join(path, "frame_rows.npy"), rows.astype(np.float64))
 
 
 def timed(sync, step, steps, warmup, settle_ms, dist=None, sync_dev=None, repeats=1):
@@ -228,9 +266,12 @@ def exit_tables(torch, vx, scene, frame, W, H):
     return info
 
 
-def single_gpu(torch, vx, scene, frame, W, H, K, steps, warmup, settle_ms, repeats=REPEATS):
-    """N = 1: K frames in flight over K streams/framebuffers; timings + stats."""
-    ex = exit_tables(torch, vx, scene, frame, W, H)
+def single_gpu(torch, vx, scene, frame, W, H, K, steps, warmup, settle_ms, repeats=REPEATS, full=True,
+               keep_last=False):
+    """N = 1: K frames in flight over K streams/framebuffers; timings + stats.
+    full: also the exit-table diagnostics and the one-stream event timing.
+    keep_last: the framebuffer of the last timed step, on the host ("last")."""
+    ex = exit_tables(torch, vx, scene, frame, W, H) if full else None
     streams = [torch.cuda.Stream() for _ in range(K)]
     torch.cuda.set_stream(streams[0])
     outs = [torch.empty(H * W * 4, dtype=torch.uint8, device="cuda") for _ in range(K)]
@@ -245,9 +286,11 @@ def single_gpu(torch, vx, scene, frame, W, H, K, steps, warmup, settle_ms, repea
         n[0] += 1
     walls, settle = timed(torch.cuda.synchronize, step, steps, warmup, settle_ms, repeats=repeats)
     med, blocks = block_summary(walls, steps)
-    ev = sorted(event_ms(torch, fns[0], steps) for _ in range(3))[1]
+    # timed() ends on a device synchronise: the last step's framebuffer is complete
+    last = outs[(n[0] - 1) % K].view(H, W, 4).cpu() if keep_last else None
+    ev = sorted(event_ms(torch, fns[0], steps) for _ in range(3))[1] if full else None
     return {"wall_s": med * steps / 1000.0, "blocks": blocks, "settle": settle, "ev_ms": ev, "stats": st.as_dict(),
-            "exit": ex}
+            "exit": ex, "last": last}
 
 
 def fps_with_d2h(torch, vx, scene, frame, W, H, frames, K=2):
@@ -418,25 +461,28 @@ def multi_rank(args, torch, dist, vx, scene, frame, W, H, K, rank, world, local,
         fns[n[0] % K]()
         n[0] += 1
     walls, settle_steps = timed(sync, step, args.steps, args.warmup, 0.0 if standin else args.settle_ms, dist,
-                                "cuda" if on_dev else None, repeats=REPEATS)
+                                "cuda" if on_dev else None, repeats=REPEATS if args.full else 1)
     tt = torch.tensor(walls, dtype=torch.float64)
     if on_dev:
         tt = tt.cuda()
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)             # per block, the slowest rank
     med, blocks = block_summary([float(v) for v in tt.cpu().tolist()], args.steps)
     wall = med * args.steps / 1000.0
-    if gloo:
+    j_last = (n[0] - 1) % K
+    last = None
+    if rank == 0 and args.dump_outputs:
+        # the frame rank 0 holds after the last timed step (timed() ends on a synchronise and a barrier)
+        last = (gs[j_last].frame if gloo else frames[j_last]).cpu().clone()
+    if gloo and args.full:
         # the rehearsal's check: rank 0's gathered frame == one whole-frame render
-        j_last = (n[0] - 1) % K
         if rank == 0:
             full = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda")
             scene.render_device(frame, full.data_ptr(), pixel_format=vx.PIXEL_RGBA8)
             torch.cuda.synchronize()
             stats["gather_frame_ok"] = bool(torch.equal(full.cpu(), gs[j_last].frame))
-    if rank == 0 and standin:
+    if rank == 0 and standin and args.full:
         # the gathered frame must hold every band's stand-in value
         from voxmap_amd.dist import band_rows_of as bro
-        j_last = (n[0] - 1) % K
         good = all(int(frames[j_last][bro(b, H, BAND)][0, 0, 0]) == (b * 7 + j_last) % 251
                    for b in range(-(-H // BAND)))
         stats["standin_frame_ok"] = bool(good)
@@ -444,56 +490,57 @@ def multi_rank(args, torch, dist, vx, scene, frame, W, H, K, rank, world, local,
     # time, max over ranks): this rank's bands rendered alone (vx_render_bands),
     # then the gather alone (collective: vx_mgpu_gather, or BandGather.gather
     # on the torch / stand-in path)
-    try:
-        if mg is not None:
-            mine = vx.mgpu_bands(H, BAND, world, rank)
-            s0 = streams[0].cuda_stream
+    if args.full:
+        try:
+            if mg is not None:
+                mine = vx.mgpu_bands(H, BAND, world, rank)
+                s0 = streams[0].cuda_stream
 
-            def r_only():
-                if mine:
-                    scene.render_bands(frame, BAND, mine, frames[0].data_ptr(), inplace=True, stream=s0)
+                def r_only():
+                    if mine:
+                        scene.render_bands(frame, BAND, mine, frames[0].data_ptr(), inplace=True, stream=s0)
 
-            def g_only():
-                mg.gather(W, H, BAND, frames[0].data_ptr(), stream=s0)
-            gbytes = int(sum(x[5] for x in vx.mgpu_transfers(W, H, BAND, world, 0)))
-        else:
-            def r_only():
-                if standin or gloo:
-                    gs[0].render()
-                else:
-                    with torch.cuda.stream(streams[0]):
+                def g_only():
+                    mg.gather(W, H, BAND, frames[0].data_ptr(), stream=s0)
+                gbytes = int(sum(x[5] for x in vx.mgpu_transfers(W, H, BAND, world, 0)))
+            else:
+                def r_only():
+                    if standin or gloo:
                         gs[0].render()
+                    else:
+                        with torch.cuda.stream(streams[0]):
+                            gs[0].render()
 
-            def g_only():
-                if standin or gloo:
-                    gs[0].gather()
-                else:
-                    with torch.cuda.stream(streams[0]):
+                def g_only():
+                    if standin or gloo:
                         gs[0].gather()
-            from voxmap_amd.dist import transfers as _tr
-            gbytes = int(sum(x[5] for x in _tr(W, H, BAND, world, 0, 4)))
-        tr, _ = timed(sync, r_only, args.steps, 2, 0.0, dist, "cuda" if on_dev else None)
-        tg, _ = timed(sync, g_only, args.steps, 2, 0.0, dist, "cuda" if on_dev else None)
-        t2 = torch.tensor([tr[0], tg[0]], dtype=torch.float64)
-        if on_dev:
-            t2 = t2.cuda()
-        dist.all_reduce(t2, op=dist.ReduceOp.MAX)
-        t2 = t2.cpu()
-        split_ms = {"render_ms": round(1000.0 * float(t2[0]) / args.steps, 4),
-                    "gather_ms": round(1000.0 * float(t2[1]) / args.steps, 4),
-                    "gather_bytes": gbytes,
-                    "how": "one stream, one frame at a time, max over ranks (the timed step overlaps "
-                           "frames in flight, so it is less than the sum)" +
-                           ("; CPU stand-in renderer, gloo gather" if standin else "")}
-    except Exception as e:                # never let the diagnostic break the bench line
-        split_ms = {"error": str(e)}
+                    else:
+                        with torch.cuda.stream(streams[0]):
+                            gs[0].gather()
+                from voxmap_amd.dist import transfers as _tr
+                gbytes = int(sum(x[5] for x in _tr(W, H, BAND, world, 0, 4)))
+            tr, _ = timed(sync, r_only, args.steps, 2, 0.0, dist, "cuda" if on_dev else None)
+            tg, _ = timed(sync, g_only, args.steps, 2, 0.0, dist, "cuda" if on_dev else None)
+            t2 = torch.tensor([tr[0], tg[0]], dtype=torch.float64)
+            if on_dev:
+                t2 = t2.cuda()
+            dist.all_reduce(t2, op=dist.ReduceOp.MAX)
+            t2 = t2.cpu()
+            split_ms = {"render_ms": round(1000.0 * float(t2[0]) / args.steps, 4),
+                        "gather_ms": round(1000.0 * float(t2[1]) / args.steps, 4),
+                        "gather_bytes": gbytes,
+                        "how": "one stream, one frame at a time, max over ranks (the timed step overlaps "
+                               "frames in flight, so it is less than the sum)" +
+                               ("; CPU stand-in renderer, gloo gather" if standin else "")}
+        except Exception as e:                # never let the diagnostic break the bench line
+            split_ms = {"error": str(e)}
     if mg is not None:
         mg.close()
     rpr = rows_per_rank(H, BAND, world)
     shards = {"unit": f"{BAND}-row full-width bands", "count": -(-H // BAND),
               "rows_per_rank_max_over_mean": round(max(rpr) / (sum(rpr) / world), 5),
               "assignment": "round-robin (band b -> rank b % N)", "gather": gather_desc, "split_ms": split_ms}
-    return stats, wall, settle_steps, shards, blocks
+    return stats, wall, settle_steps, shards, blocks, last
 
 
 # ---------------------------------------------------------------- main
@@ -548,7 +595,8 @@ def main(argv=None):
     if not standin:
         grid = presets.scene_grid(cfg["scene"])
         Z, Y, X = grid.shape
-        noise = scenes.real_noise()            # the reference's res/noise.bin.gz (u_noise, render.js:138)
+        if args.full and world == 1 and not args.no_cpu:
+            noise = scenes.real_noise()        # the reference's res/noise.bin.gz (u_noise, render.js:138)
         t_scene = time.perf_counter()
         # palette grid in, distance field + octant copies built on the device (f-1);
         # the noise texture through the product's .gz loader
@@ -560,17 +608,21 @@ def main(argv=None):
     shards = None
     exit_info = None
     if world == 1:
-        r = single_gpu(torch, vx, scene, frame, W, H, K, args.steps, args.warmup, args.settle_ms)
+        r = single_gpu(torch, vx, scene, frame, W, H, K, args.steps, args.warmup, args.settle_ms,
+                       repeats=REPEATS if args.full else 1, full=args.full, keep_last=bool(args.dump_outputs))
         stats, wall, settle_steps, ev_ms = r["stats"], r["wall_s"], r["settle"], r["ev_ms"]
-        exit_info, blocks = r["exit"], r["blocks"]
+        exit_info, blocks, last = r["exit"], r["blocks"], r["last"]
     else:
-        stats, wall, settle_steps, shards, blocks = multi_rank(args, torch, dist, vx, scene, frame, W, H, K, rank,
-                                                               world, local, standin)
+        stats, wall, settle_steps, shards, blocks, last = multi_rank(args, torch, dist, vx, scene, frame, W, H, K,
+                                                                     rank, world, local, standin)
         ev_ms = None
     ms_per_step = 1000.0 * wall / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    del last
 
     v1 = c5 = d2h = None
-    if world == 1 and flags != 0 and args.flags is None and samples <= 1:
+    if args.full and world == 1 and flags != 0 and args.flags is None and samples <= 1:
         # the reference's own shader (v1, flags 0) on the same frame: the same
         # K-in-flight wall timing, and one stream with events for its roofline
         fr1 = presets.camera_frame(cam, W, H, scale=up)
@@ -582,9 +634,10 @@ def main(argv=None):
               "single_stream_ms_per_frame": round(a["ev_ms"], 4), "alg_bytes": int(s1["alg_bytes"]),
               "roofline_frac": round(roofline_of(s1["alg_bytes"], a["ev_ms"])[1], 4),
               "lane_util": lane_utils(s1), "exit_tables": a["exit"]}
-    if world == 1 and not args.no_d2h:
+    if args.full and world == 1 and not args.no_d2h:
         d2h = fps_with_d2h(torch, vx, scene, frame, W, H, max(20, args.steps // 2))
-    if world == 1 and cfg_name == "C3" and not args.no_c5 and args.flags is None and args.samples is None:
+    if (args.full and world == 1 and cfg_name == "C3" and not args.no_c5 and args.flags is None
+            and args.samples is None):
         # BASELINE configs[4] in the same run (C5 next to C3)
         c5cfg = presets.CONFIGS["C5"]
         g5 = presets.scene_grid(c5cfg["scene"])
@@ -631,7 +684,8 @@ def main(argv=None):
               "exit_tables": b["exit"]}
         sc5.close()
     c3ra = None
-    if world == 1 and cfg_name == "C3" and flags == vx.FLAG_FULL_QUALITY and args.flags is None and samples <= 1:
+    if (args.full and world == 1 and cfg_name == "C3" and flags == vx.FLAG_FULL_QUALITY and args.flags is None
+            and samples <= 1):
         # a reflection workload over the whole frame -- every first
         # surface traces its mirror ray (VX_FLAG_REFLECT_ALL), next to the headline
         fra = presets.camera_frame(cam, W, H, scale=up, flags=flags | vx.FLAG_REFLECT_ALL)
@@ -657,6 +711,8 @@ def main(argv=None):
     if rank == 0:
         per_launch_bytes = float(stats["alg_bytes"]) / world if world > 1 else float(stats["alg_bytes"])
         kernel_ms = ev_ms if world == 1 else stats["kernel_ms"]
+        # a plain N = 1 run takes no one-stream timing: the roofline figures are --full's
+        measured = kernel_ms is not None
         achieved, frac = roofline_of(per_launch_bytes, kernel_ms) if kernel_ms else (0.0, 0.0)
         tag = PMC_TAG if cfg_name != "C5" else f"{PMC_TAG}_c5"
         traffic = pmc_entry(f"traffic_{tag}.json", cfg_name, cam, flags, samples) if world == 1 else None
@@ -677,6 +733,7 @@ def main(argv=None):
             "value": round(value, 3),
             "unit": "Mrays/s",
             "n_gpus": world,
+            "full": bool(args.full),
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 4),
@@ -733,15 +790,15 @@ def main(argv=None):
                 "bound": bound_of(valu),
                 "kernel": "k_render (fused primary visibility + shading + sun march" +
                           (" + reflection walk" if flags & vx.FLAG_REFLECT else "") + ")",
-                "achieved": round(achieved, 2),
+                "achieved": round(achieved, 2) if measured else None,
                 "peak": HBM_PEAK_GBPS,
                 "unit": "GB/s",
-                "frac": round(frac, 4),
+                "frac": round(frac, 4) if measured else None,
                 "traffic": traffic.get("hbm_bytes_per_launch") if traffic else None,
                 "alg_bytes_per_launch": int(per_launch_bytes),
                 "avg_launch_ms": round(kernel_ms, 4) if kernel_ms else None,
                 "fabric_gbps": (round(traffic["hbm_bytes_per_launch"] / (kernel_ms * 1e-3) / 1e9, 1)
-                                if traffic else None),
+                                if traffic and kernel_ms else None),
                 "valu": ({k: valu[k] for k in ("valu_busy", "valu_lane_util", "valu_insts_per_wave", "clock_ghz",
                                                "source") if k in valu} if valu else None),
                 "texture_path": ({k: valu[k] for k in ("ta_busy", "td_busy") if valu.get(k) is not None}
@@ -752,7 +809,7 @@ def main(argv=None):
             result["config"]["standin_frame_ok"] = stats.get("standin_frame_ok")
         if "gather_frame_ok" in stats:
             result["config"]["gather_frame_ok"] = stats["gather_frame_ok"]
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             result["cpu_baseline"] = cpu_baseline(scene, noise, frame, W, H, args.cpu_seconds)
     if scene is not None:
         scene.close()

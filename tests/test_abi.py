@@ -1,6 +1,7 @@
 """CPU tests of the C ABI (no GPU compute): symbols, error paths, codecs,
 field builder parity with the literal restatements, camera/sun helpers."""
 import gzip
+import hashlib
 import math
 import os
 import re
@@ -11,7 +12,10 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+# SHA-256 of the reference's own assets (res/map.blob = src/map.blob, res/noise.bin.gz), recorded from it
+MAP_BLOB_SHA = "22114bbc9a1e12ade6c2d3e8d42c1f3f2dcd605f7e7be1010cfef6a885285701"
+NOISE_GZ_SHA = "7e6ca94cfcb8ce582e7b93e803eab8ee7049202e9c20586ebc5fc00df3ca9253"
 
 
 def test_library_exports_every_header_symbol(built):
@@ -82,24 +86,28 @@ def test_blob_round_trip_and_fixed_iv_against_openssl_cli(built, tmp_path):
     assert e.value.code in (-3, -4)
 
 
-@pytest.mark.skipif(not os.path.exists(f"{REF}/res/map.blob"), reason="reference assets absent")
 def test_real_map_blob_size_pins_and_rejects_wrong_key(built):
-    """res/map.blob: 543,824 B = 33,989 AES blocks; the key is not in
-    the repository, so decoding with any test key must fail cleanly."""
+    """res/map.blob (tests/golden/map.blob, a byte copy; the reference's
+    src/map.blob is the same file): 543,824 B = 33,989 AES blocks (SURVEY §4);
+    the key is not in the repository, so decoding with any test key must fail
+    cleanly."""
     import voxmap_amd as vx
-    blob = open(f"{REF}/res/map.blob", "rb").read()
+    blob = open(os.path.join(GOLDEN, "map.blob"), "rb").read()
     assert len(blob) == 543824 and len(blob) % 16 == 0
-    assert open(f"{REF}/src/map.blob", "rb").read() == blob
+    assert hashlib.sha256(blob).hexdigest() == MAP_BLOB_SHA
     with pytest.raises(vx.VoxmapError) as e:
         vx.decode(blob, vx.FORMAT_BLOB, key=KEY)
     assert e.value.code in (-3, -4)
 
 
-@pytest.mark.skipif(not os.path.exists(f"{REF}/res/noise.bin.gz"), reason="reference assets absent")
 def test_real_noise_asset_decodes(built):
-    """res/noise.bin.gz: 1024x1024 RGBA8 (render.js:141); A channel in 0..240, mean ~128."""
+    """res/noise.bin.gz (shipped as voxmap_amd/data/noise.bin.gz, a byte copy):
+    1024x1024 RGBA8 (render.js:141); A channel in 0..240, mean ~128."""
     import voxmap_amd as vx
-    raw = vx.decode(open(f"{REF}/res/noise.bin.gz", "rb").read(), vx.FORMAT_BIN_GZ)
+    from voxmap_amd import scenes
+    blob = open(scenes.NOISE_PATH, "rb").read()
+    assert hashlib.sha256(blob).hexdigest() == NOISE_GZ_SHA
+    raw = vx.decode(blob, vx.FORMAT_BIN_GZ)
     assert len(raw) == 1024 * 1024 * 4
     a = np.frombuffer(raw, np.uint8).reshape(1024, 1024, 4)[..., 3]
     assert a.min() == 0 and a.max() == 240 and abs(a.mean() - 128.0) < 0.5

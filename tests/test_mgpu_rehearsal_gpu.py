@@ -27,7 +27,8 @@ def test_two_ranks_on_one_gpu_gather_the_frame(built):
         env.pop(k, None)
     env["VOXMAP_BENCH_DEVICE"] = "0"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--gather", "gloo",
-                        "--config", "C4", "--steps", "2", "--warmup", "1", "--inflight", "2", "--settle-ms", "0"],
+                        "--full", "--config", "C4", "--steps", "2", "--warmup", "1", "--inflight", "2",
+                        "--settle-ms", "0"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -89,12 +89,14 @@ def test_real_noise_fixture_checksums_and_texels(built):
     assert np.array_equal(scenes.real_noise(), a)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/res/noise.bin.gz"), reason="reference absent")
 def test_fixtures_are_the_reference_assets():
-    """In the build container: the shipped fixtures are byte copies of the reference's assets."""
+    """The shipped fixtures are byte copies of the reference's assets: their sizes
+    and SHA-256 are those of its res/noise.bin.gz and res/vertex2d.bin.gz,
+    recorded from the reference itself."""
     from voxmap_amd import scenes
-    assert open(scenes.NOISE_PATH, "rb").read() == open("/root/reference/res/noise.bin.gz", "rb").read()
-    assert open(V2D, "rb").read() == open("/root/reference/res/vertex2d.bin.gz", "rb").read()
+    noise, v2d = open(scenes.NOISE_PATH, "rb").read(), open(V2D, "rb").read()
+    assert len(noise) == 4169744 and hashlib.sha256(noise).hexdigest() == NOISE_GZ_SHA
+    assert len(v2d) == 43356 and hashlib.sha256(v2d).hexdigest() == V2D_SHA
 
 
 def test_vertex2d_regenerated_from_the_campus_map(built, v2d):

@@ -16,6 +16,6 @@ cd "$ROOT" || exit 1
 python tools/prof_summary2.py $TAG C3 K1 48 1 > "$OUT/summary_c3.txt" 2>&1 || exit 1
 python tools/prof_summary2.py ${TAG}_c5 C5 K1 48 16 > "$OUT/summary_c5.txt" 2>&1 || exit 1
 cp profiles/*${TAG}* "$OUT/" || exit 1
-timeout -k 10 400 python bench.py > "$OUT/bench.log" 2>&1 || { echo "bench failed rc=$?"; tail -20 "$OUT/bench.log"; exit 1; }
+timeout -k 10 400 python bench.py --full > "$OUT/bench.log" 2>&1 || { echo "bench failed rc=$?"; tail -20 "$OUT/bench.log"; exit 1; }
 tail -1 "$OUT/bench.log"
 echo "final measure done ($TAG)"

@@ -7,10 +7,13 @@ ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$ROOT" || exit 1
 mkdir -p gpurun_out
 TAG="${TAG:-r01}"
-timeout -k 10 300 python bench.py > gpurun_out/bench_c3.log 2>&1 || { echo "bench C3 failed rc=$?"; tail -20 gpurun_out/bench_c3.log; exit 1; }
-tail -1 gpurun_out/bench_c3.log
-timeout -k 10 300 python bench.py --config C5 > gpurun_out/bench_c5.log 2>&1 || { echo "bench C5 failed rc=$?"; tail -20 gpurun_out/bench_c5.log; exit 1; }
-tail -1 gpurun_out/bench_c5.log
+# the bench logs go to $MEASURE_OUT (default measure_out/ in the repository root)
+LOGS="${MEASURE_OUT:-$ROOT/measure_out}"
+mkdir -p "$LOGS"
+timeout -k 10 300 python bench.py --full > "$LOGS/bench_c3.log" 2>&1 || { echo "bench C3 failed rc=$?"; tail -20 "$LOGS/bench_c3.log"; exit 1; }
+tail -1 "$LOGS/bench_c3.log"
+timeout -k 10 300 python bench.py --full --config C5 > "$LOGS/bench_c5.log" 2>&1 || { echo "bench C5 failed rc=$?"; tail -20 "$LOGS/bench_c5.log"; exit 1; }
+tail -1 "$LOGS/bench_c5.log"
 [ "${SKIP_PROF:-0}" = 1 ] && exit 0
 # one frame in flight under the profiler: kernel durations not stretched by
 # overlap, so rocprofv3's average matches the bench's roofline.avg_launch_ms
