@@ -34,7 +34,9 @@ extern "C" {
  * canvas byte with clamped source and alpha (render.js:84-86, map.js:7), band /
  * tile lists are cached per distinct list, no caller stream handle is kept,
  * a zeroed dist_cap falls back to VX_FALLBACK_DIST_CAP where 64 does not fit,
- * and the sun march reads the doom table (VX_FLAG_NO_DOOM: without). */
+ * and the sun march reads the doom table (VX_FLAG_NO_DOOM: without).
+ * Still ABI 10, additive only: the ray queries (vx_query_rays, vx_pixel_ray,
+ * vx_place_rays and their structs) change no existing signature or layout. */
 #define VX_ABI_VERSION 10
 
 /* error codes */
@@ -302,6 +304,69 @@ int vx_render_bands(vx_scene *scene, const vx_frame_params *p, int w, int h, int
                     const int *band_ids, int n_bands, int pixel_format, void *out_device,
                     int inplace, void *stream, vx_stats *stats);
 
+/* --- ray queries: picking and place-label visibility (DESIGN.md "Ray queries") ---
+ * The reference's page labels every place without asking whether a building
+ * hides it (drawOverlay, map.js:102-164; the empty loop at :157-159) and drags
+ * over an assumed flat ground (projectToGround, map.js:200-205).  A batch of
+ * rays walks the field copies the primary traversal uses and returns, per ray,
+ * what the frame's primary visibility would: the first surface, with the glass
+ * pane in front of it if there is one.
+ *
+ * A ray is origin + t * dir, the origin split as the camera's is; dir need not
+ * be normalised and t is in units of dir.  A surface is an entry into a cell
+ * of palette index 1..21 from a cell of another index.  The first glass entry
+ * is recorded and passed, later glass entries are passed, the first other
+ * entry ends the walk: 0, 1 or 2 records, in ray order, each the unit-cell
+ * G-buffer record of VX_FLAG_UNIT_GBUF.  t_max: the walk ends at the first
+ * step whose crossing time is >= t_max, so only records with t < t_max
+ * (strict, fp32) are returned; INFINITY walks to the end.
+ *
+ * The kernel checks every ray itself and answers n = VX_RAY_INVALID without
+ * walking for |cell| >= 2^22 on an axis, a fract outside [0, 1), a non-finite
+ * or all-zero dir, or a NaN t_max.  No ray makes it read out of bounds. */
+#define VX_RAY_INVALID (-1)
+#define VX_MAX_QUERY_RAYS (1 << 26)
+typedef struct vx_ray {            /* 48 bytes; device arrays 16-byte aligned */
+    int32_t cell[3];               /* floor(origin), as u_cellPos */
+    float   fract[3];              /* origin - cell, 0 <= f < 1, as u_fractPos */
+    float   dir[3];                /* need not be normalised; t is in units of dir */
+    float   t_max;                 /* records with t >= t_max are dropped; INFINITY = none */
+    uint32_t reserved[2];          /* 0 */
+} vx_ray;
+typedef struct vx_surface {        /* the unit-cell G-buffer record (VX_FLAG_UNIT_GBUF's split) */
+    int32_t id, color, normal_idx; /* id 0 block / 2 glass; palette index; render.vert:14-17 */
+    int32_t cell[3];               /* entered cell; on the face axis its plane */
+    float   fract[3];              /* hit point minus cell (0 on the face axis) */
+    float   t;
+} vx_surface;
+/* n = 2: glass in s[0], what lies behind it in s[1]; n = 1: an opaque surface,
+ * or glass with sky behind it; n = 0: a miss; n = VX_RAY_INVALID.  Records
+ * past n are zero. */
+typedef struct vx_ray_hit {
+    int32_t n;
+    uint32_t reserved;
+    vx_surface s[2];
+} vx_ray_hit;
+/* hits: records returned, glass: those with id 2; fetches: field texels read,
+ * equal to the oracle's count (vxo_primary) only when every ray has t_max =
+ * INFINITY, since t_max ends a walk early; cap_hits must be 0. */
+typedef struct vx_query_stats {
+    uint64_t rays, invalid, hits, glass, fetches, cap_hits;
+    double kernel_ms;
+} vx_query_stats;
+/* n rays in, n results out.  on_device != 0: both arrays are device pointers
+ * on the scene's GPU (rays 16-byte aligned, hits 4-byte), the call is
+ * stream-ordered and does not synchronise.  Otherwise they are host arrays:
+ * the call stages them through stream-ordered allocations on `stream`, copies
+ * back and synchronises that stream only.  n == 0 does nothing; n < 0, n >
+ * VX_MAX_QUERY_RAYS or a NULL scene or array is VX_EINVAL before any GPU call.
+ * stream NULL: the scene's own.  Calls may run concurrently on different
+ * streams of one scene, beside vx_render*; calls that ask for stats follow
+ * vx_render's rule: they share the scene's counters and events, are
+ * serialised per scene by the caller, and synchronise the stream. */
+int vx_query_rays(vx_scene *scene, const vx_ray *rays, int n, vx_ray_hit *hits,
+                  int on_device, void *stream, vx_query_stats *stats);
+
 /* --- one frame across the GPUs of a node (RCCL over xGMI) -----
  * Replaces nothing in the reference (one browser GPU); SURVEY §8(e).  One
  * process (or thread) per GPU, each with its own vx_scene of the same map.
@@ -356,6 +421,27 @@ int vx_mgpu_transfers(int w, int h, int band_rows, int pixel_format, int nranks,
 int vx_frame_from_orbit(const double sbj[3], const double rot[3], int w, int h, vx_frame_params *p);
 /* Same from a column-major u_matrix (render.js:288) and camera position. */
 int vx_frame_from_matrix(const float u_matrix[16], const double cam_pos[3], vx_frame_params *p);
+/* The view ray of pixel (px, py) of a w*h frame of p as a query ray: the
+ * frame's camera split as the origin, dir = fwd + nx*right + ny*up by the
+ * formula above (fp32, that order), t_max = INFINITY.  px, py, w or h out of
+ * range: VX_EINVAL.  A pure host function. */
+int vx_pixel_ray(const vx_frame_params *p, int w, int h, int px, int py, vx_ray *out);
+/* drawOverlay's projection of the places (map.js:117-137, math.js m4.v4, in
+ * double as the page computes it): view = u_matrix * (x, y, z, 1), ndc = view.xy
+ * / view.w, distance = |place - cam_pos|; on_screen is the page's own test
+ * (map.js:121, 127): not (w < 0), not (|ndc_x| > 1.1), not (|ndc_y| > 1.1).
+ * And per place the ray camera -> place: the origin split as
+ * vx_frame_from_matrix splits cam_pos, dir = (float)(place - cam_pos), t_max
+ * = 1, so a record is a surface strictly between the camera and the place.
+ * Visibility rule: a place is hidden iff the result of its ray holds an
+ * opaque record (id == 0) among s[0..n); glass hides nothing.  views or rays
+ * may be NULL.  A pure host function. */
+typedef struct vx_place_view {
+    float ndc_x, ndc_y, w, distance;
+    int32_t on_screen;
+} vx_place_view;
+int vx_place_rays(const float u_matrix[16], const double cam_pos[3], const double (*places)[3], int n,
+                  vx_place_view *views, vx_ray *rays);
 /* map.js:399-402: hour -> sun direction. */
 void vx_sun_from_hour(double hour, float sun[3]);
 /* The soft-shadow sun directions a frame with shadow_samples = n uses

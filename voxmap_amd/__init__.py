@@ -10,7 +10,9 @@ from ._abi import (FLAG_GLASS_ORDER, FLAG_GLASS_SINGLE, FLAG_REFLECT_ALL, FLAG_U
                    FrameParams, Stats, VoxmapError, lib)
 from .renderer import (Frame, MultiGPU, Scene, blob_encrypt, decode, field_build, frame_from_matrix, frame_from_orbit,
                        hour_from_time_ms, make_frame, mgpu_band_rows, mgpu_bands, mgpu_transfers, mgpu_unique_id, noise_synth, field_build_gpu,
-                       params_to_dict, sun_from_hour, sun_samples, vertex2d)
+                       params_to_dict, sun_from_hour, sun_samples, vertex2d,
+                       HIT_DTYPE, PLACE_VIEW_DTYPE, RAY_DTYPE, SURFACE_DTYPE, hits_visible, pixel_ray, place_rays)
+from ._abi import QueryStats, RAY_INVALID
 
 __all__ = [
     "Scene", "Frame", "FrameParams", "Stats", "VoxmapError", "lib", "make_frame", "frame_from_orbit",
@@ -20,4 +22,6 @@ __all__ = [
     "FLAG_REFLECT", "FLAG_ROUGH", "FLAG_FULL_QUALITY", "FLAG_INT_INDEX", "FLAG_SOFT_POOL", "FLAG_SOFT_BRICK", "FLAG_NO_EXIT", "FLAG_NO_CONE", "FLAG_NO_DOOM",
     "FLAG_UNIT_GBUF", "FLAG_GLASS_ORDER", "FLAG_GLASS_SINGLE", "FLAG_REFLECT_ALL", "sun_samples", "field_build_gpu", "FORMAT_GRID",
     "MultiGPU", "mgpu_unique_id", "mgpu_band_rows", "mgpu_bands", "mgpu_transfers", "vertex2d",
+    "RAY_DTYPE", "HIT_DTYPE", "SURFACE_DTYPE", "PLACE_VIEW_DTYPE", "QueryStats", "RAY_INVALID", "pixel_ray",
+    "place_rays", "hits_visible",
 ]

@@ -98,6 +98,41 @@ class ExitInfo(C.Structure):
     _fields_ = [("kind", C.c_int), ("octant", C.c_int), ("kx", C.c_int), ("ky", C.c_int), ("build_ms", C.c_float)]
 
 
+RAY_INVALID = -1
+MAX_QUERY_RAYS = 1 << 26
+
+
+class Ray(C.Structure):
+    """vx_ray: origin cell + fract, direction, t_max."""
+    _fields_ = [("cell", C.c_int32 * 3), ("fract", C.c_float * 3), ("dir", C.c_float * 3), ("t_max", C.c_float),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class Surface(C.Structure):
+    """vx_surface: the unit-cell G-buffer record of one surface along a ray."""
+    _fields_ = [("id", C.c_int32), ("color", C.c_int32), ("normal_idx", C.c_int32), ("cell", C.c_int32 * 3),
+                ("fract", C.c_float * 3), ("t", C.c_float)]
+
+
+class RayHit(C.Structure):
+    """vx_ray_hit: n = -1 invalid, 0 miss, 1, 2 records."""
+    _fields_ = [("n", C.c_int32), ("reserved", C.c_uint32), ("s", Surface * 2)]
+
+
+class QueryStats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("invalid", C.c_uint64), ("hits", C.c_uint64), ("glass", C.c_uint64),
+                ("fetches", C.c_uint64), ("cap_hits", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class PlaceView(C.Structure):
+    """vx_place_view: drawOverlay's projection of one place (map.js:117-137)."""
+    _fields_ = [("ndc_x", C.c_float), ("ndc_y", C.c_float), ("w", C.c_float), ("distance", C.c_float),
+                ("on_screen", C.c_int32)]
+
+
 # (name, restype, argtypes) of every symbol include/voxmap.h declares
 SIGNATURES = [
     ("vx_scene_create", C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_void_p)]),
@@ -143,6 +178,11 @@ SIGNATURES = [
                               C.POINTER(C.c_size_t)]),
     ("vx_noise_synth", C.c_int, [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     ("vx_field_build_gpu", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    ("vx_query_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                C.POINTER(QueryStats)]),
+    ("vx_pixel_ray", C.c_int, [C.POINTER(FrameParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Ray)]),
+    ("vx_place_rays", C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_void_p, C.c_int, C.c_void_p,
+                                C.c_void_p]),
     ("vx_last_error", C.c_char_p, []),
     ("vx_abi_version", C.c_int, []),
 ]

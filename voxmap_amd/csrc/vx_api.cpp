@@ -675,6 +675,76 @@ int vx_render(vx_scene *s, const vx_frame_params *p, int w, int h, int fmt, void
     return rc;
 }
 
+// One k_query launch over device arrays.  It reads only what vx_scene_create
+// left behind (the octant copies and their layout), so it takes no scene lock;
+// with stats it uses the scene's counters and events, as a vx_render with stats.
+static int do_query(vx_scene *s, const void *d_rays, int n, void *d_hits, hipStream_t st, vx_query_stats *stats) {
+    QueryArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.prim = s->d_prim;
+    a.rays = d_rays;
+    a.hits = d_hits;
+    a.X = s->X; a.Y = s->Y; a.Z = s->Z;
+    a.pad = s->L.pad;
+    a.Xp = s->L.Xp;
+    a.XpYp = (unsigned)s->L.Xp * (unsigned)s->L.Yp;
+    a.copy_texels = (unsigned)s->L.texels;
+    a.n = n;
+    if (stats) {
+        a.stats = s->d_stats;
+        VX_HIP(hipMemsetAsync(s->d_stats, 0, sizeof(unsigned long long) * QS_COUNT, st));
+        VX_HIP(hipEventRecord(s->ev0, st));
+    }
+    const int rc = launch_query(a, st);
+    if (rc) return set_error(VX_EDEVICE, std::string("query launch failed: ") + hipGetErrorString((hipError_t)rc));
+    if (stats) {
+        VX_HIP(hipEventRecord(s->ev1, st));
+        unsigned long long v[QS_COUNT];
+        VX_HIP(hipMemcpyAsync(v, s->d_stats, sizeof v, hipMemcpyDeviceToHost, st));
+        VX_HIP(hipStreamSynchronize(st));
+        float ms = 0.0f;
+        VX_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+        stats->rays = (uint64_t)n;
+        stats->invalid = v[QS_INVALID];
+        stats->hits = v[QS_HITS];
+        stats->glass = v[QS_GLASS];
+        stats->fetches = v[QS_FETCH];
+        stats->cap_hits = v[QS_CAP_HITS];
+        stats->kernel_ms = ms;
+    }
+    return VX_OK;
+}
+
+int vx_query_rays(vx_scene *s, const vx_ray *rays, int n, vx_ray_hit *hits, int on_device, void *stream,
+                  vx_query_stats *stats) {
+    if (!s || !rays || !hits) return set_error(VX_EINVAL, "vx_query_rays: null argument");
+    if (n < 0 || n > VX_MAX_QUERY_RAYS) return set_error(VX_EINVAL, "vx_query_rays: n out of range (0 .. 2^26)");
+    if (on_device && (((uintptr_t)rays & 15u) || ((uintptr_t)hits & 3u)))
+        return set_error(VX_EINVAL, "vx_query_rays: device rays must be 16-byte aligned, hits 4-byte");
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n == 0) return VX_OK;
+    VX_HIP(hipSetDevice(s->device));
+    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+    if (on_device) return do_query(s, rays, n, hits, st, stats);
+    const size_t rb = (size_t)n * sizeof(vx_ray), hb = (size_t)n * sizeof(vx_ray_hit);
+    void *d_r = nullptr, *d_h = nullptr;
+    int rc = VX_OK;
+    hipError_t e = hipMallocAsync(&d_r, rb, st);
+    if (e == hipSuccess) e = hipMallocAsync(&d_h, hb, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_r, rays, rb, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) rc = set_error(VX_EDEVICE, std::string("query staging failed: ") + hipGetErrorString(e));
+    if (rc == VX_OK) rc = do_query(s, d_r, n, d_h, st, stats);
+    if (rc == VX_OK) {
+        e = hipMemcpyAsync(hits, d_h, hb, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = set_error(VX_EDEVICE, std::string("query readback failed: ") + hipGetErrorString(e));
+    }
+    if (d_r) (void)hipFreeAsync(d_r, st);
+    if (d_h) (void)hipFreeAsync(d_h, st);
+    (void)hipStreamSynchronize(st);
+    return rc;
+}
+
 }  // extern "C"
 
 // Tile / band-id lists live on the device, uploaded once per distinct list

@@ -284,6 +284,60 @@ int vx_frame_from_matrix(const float m[16], const double cam_pos[3], vx_frame_pa
     return VX_OK;
 }
 
+// ---- query rays (host halves: no GPU) -------------------------------------
+int vx_pixel_ray(const vx_frame_params *p, int w, int h, int px, int py, vx_ray *out) {
+    if (!p || !out) return set_error(VX_EINVAL, "vx_pixel_ray: null argument");
+    if (w <= 0 || h <= 0 || w > 32768 || h > 32768 || px < 0 || py < 0 || px >= w || py >= h)
+        return set_error(VX_EINVAL, "vx_pixel_ray: pixel or frame size out of range");
+    // the header's formula, fp32, this operation order (the kernel's and the oracle's vxo_pixel_dir)
+    const float nx = (float)(2 * px + 1) / (float)w - 1.0f;
+    const float ny = 1.0f - (float)(2 * py + 1) / (float)h;
+    std::memset(out, 0, sizeof *out);
+    for (int i = 0; i < 3; i++) {
+        out->cell[i] = p->cam_cell[i];
+        out->fract[i] = p->cam_fract[i];
+        out->dir[i] = (p->ray_fwd[i] + nx * p->ray_right[i]) + ny * p->ray_up[i];
+    }
+    out->t_max = INFINITY;
+    return VX_OK;
+}
+
+int vx_place_rays(const float m[16], const double cam_pos[3], const double (*places)[3], int n, vx_place_view *views,
+                  vx_ray *rays) {
+    if (!m || !cam_pos || (n > 0 && !places)) return set_error(VX_EINVAL, "vx_place_rays: null argument");
+    if (n < 0) return set_error(VX_EINVAL, "vx_place_rays: n < 0");
+    vx_frame_params cam;                              // the origin split of vx_frame_from_matrix
+    set_cam(cam_pos, &cam);
+    for (int k = 0; k < n; k++) {
+        const double *q = places[k];
+        if (views) {
+            // math.js:106-135 m4.v4 (column-major, summed left to right), map.js:117-137
+            double v[4];
+            for (int r = 0; r < 4; r++)
+                v[r] = (double)m[r] * q[0] + (double)m[4 + r] * q[1] + (double)m[8 + r] * q[2] + (double)m[12 + r] * 1.0;
+            const double x = v[0] / v[3], y = v[1] / v[3];
+            const double dx = q[0] - cam_pos[0], dy = q[1] - cam_pos[1], dz = q[2] - cam_pos[2];
+            vx_place_view &o = views[k];
+            o.ndc_x = (float)x;
+            o.ndc_y = (float)y;
+            o.w = (float)v[3];
+            o.distance = (float)std::sqrt(((0.0 + dx * dx) + dy * dy) + dz * dz);   // math.js:29 reduce from 0
+            o.on_screen = (!(v[3] < 0.0) && !(std::fabs(x) > 1.1) && !(std::fabs(y) > 1.1)) ? 1 : 0;
+        }
+        if (rays) {
+            vx_ray &r = rays[k];
+            std::memset(&r, 0, sizeof r);
+            for (int i = 0; i < 3; i++) {
+                r.cell[i] = cam.cam_cell[i];
+                r.fract[i] = cam.cam_fract[i];
+                r.dir[i] = (float)(q[i] - cam_pos[i]);
+            }
+            r.t_max = 1.0f;
+        }
+    }
+    return VX_OK;
+}
+
 void vx_sun_from_hour(double hour, float sun[3]) {   // map.js:399-402
     sun[0] = (float)(std::sin(hour) * std::sqrt(3.0 / 4.0));
     sun[1] = (float)(std::sin(hour) * std::sqrt(1.0 / 4.0));

@@ -224,6 +224,21 @@ size_t vertex2d_bytes(const std::vector<Quad2d> &quads, uint8_t *out, size_t cap
 // c2d (X*Y, x fastest) of the upload after launch_field_vis: vis colour of each column's top block, z >= 1
 int launch_footprint(const uint32_t *lin, uint8_t *c2d, int X, int Y, int Z, void *stream);
 
+// Parameters of one ray-query launch (vx_query.hip; passed by value, a few
+// words: nothing for the compiler to copy to scratch).
+struct QueryArgs {
+    const uint32_t *prim;    // the 8 padded octant copies (KernelArgs::prim)
+    const void *rays;        // n vx_ray, 16-byte aligned
+    void *hits;              // n vx_ray_hit
+    unsigned long long *stats;   // QS_COUNT device counters, or nullptr
+    int X, Y, Z;
+    int pad, Xp;             // FieldLayout::pad, ::Xp
+    unsigned XpYp, copy_texels;
+    int n;
+};
+enum QueryStatSlot { QS_INVALID = 0, QS_HITS, QS_GLASS, QS_FETCH, QS_CAP_HITS, QS_COUNT };
+int launch_query(const QueryArgs &a, void *stream);
+
 // Launchers (vx_kernels.hip).  Return a hipError_t as int.
 int launch_render(const KernelArgs &a, int pixel_format, void *stream);
 int launch_detile(const void *tiles, void *frame, int w, int h, int tile_size, int tiles_x,

@@ -91,6 +91,44 @@ def sun_samples(sun, radius: float, n: int):
     return out
 
 
+# ---- ray queries (vx_query_rays): structured numpy mirrors of vx_ray / vx_ray_hit ----
+RAY_DTYPE = np.dtype([("cell", np.int32, 3), ("fract", np.float32, 3), ("dir", np.float32, 3),
+                      ("t_max", np.float32), ("reserved", np.uint32, 2)])
+SURFACE_DTYPE = np.dtype([("id", np.int32), ("color", np.int32), ("normal_idx", np.int32), ("cell", np.int32, 3),
+                          ("fract", np.float32, 3), ("t", np.float32)])
+HIT_DTYPE = np.dtype([("n", np.int32), ("reserved", np.uint32), ("s", SURFACE_DTYPE, 2)])
+PLACE_VIEW_DTYPE = np.dtype([("ndc_x", np.float32), ("ndc_y", np.float32), ("w", np.float32),
+                             ("distance", np.float32), ("on_screen", np.int32)])
+
+
+def pixel_ray(frame: "Frame", px: int, py: int) -> np.ndarray:
+    """The view ray of pixel (px, py) of ``frame`` as one RAY_DTYPE record (vx_pixel_ray)."""
+    out = np.zeros(1, RAY_DTYPE)
+    check(lib().vx_pixel_ray(C.byref(frame.params), frame.width, frame.height, int(px), int(py),
+                             C.cast(out.ctypes.data, C.POINTER(_abi.Ray))))
+    return out[0]
+
+
+def place_rays(u_matrix, cam_pos, places):
+    """drawOverlay's projection of ``places`` (n x 3, map.js:117-137) and the rays camera ->
+    place with t_max = 1 (vx_place_rays): (views[n] PLACE_VIEW_DTYPE, rays[n] RAY_DTYPE)."""
+    pl = np.ascontiguousarray(np.asarray(places, dtype=np.float64).reshape(-1, 3))
+    n = int(pl.shape[0])
+    views, rays = np.zeros(n, PLACE_VIEW_DTYPE), np.zeros(n, RAY_DTYPE)
+    m = (C.c_float * 16)(*[float(v) for v in u_matrix])
+    pos = (C.c_double * 3)(*cam_pos)
+    check(lib().vx_place_rays(m, pos, pl.ctypes.data, n, views.ctypes.data, rays.ctypes.data))
+    return views, rays
+
+
+def hits_visible(hits: np.ndarray) -> np.ndarray:
+    """The header's visibility rule per result: hidden iff an opaque record (id == 0) is among s[0..n)."""
+    n = hits["n"]
+    ids = hits["s"]["id"]
+    hidden = ((n >= 1) & (ids[:, 0] == 0)) | ((n >= 2) & (ids[:, 1] == 0))
+    return ~hidden
+
+
 class Scene:
     """Device-resident field + noise textures on one GPU (render.js:134-206)."""
 
@@ -241,6 +279,38 @@ class Scene:
         check(lib().vx_detile(self.handle, int(w), int(h), int(tile_size), ids.ctypes.data_as(C.POINTER(C.c_int)),
                               int(ids.size), pixel_format, C.c_void_p(tiles_ptr), C.c_void_p(frame_ptr),
                               C.c_void_p(stream) if stream else None))
+
+    def query_rays(self, rays: np.ndarray, *, stats: bool = False):
+        """Walk a batch of rays (RAY_DTYPE, host) through the scene: HIT_DTYPE results in ray
+        order, and the call's QueryStats when ``stats`` (vx_query_rays)."""
+        r = np.ascontiguousarray(np.asarray(rays, dtype=RAY_DTYPE).reshape(-1))
+        out = np.zeros(r.size, HIT_DTYPE)
+        st = _abi.QueryStats() if stats else None
+        if r.size:
+            check(lib().vx_query_rays(self.handle, r.ctypes.data, int(r.size), out.ctypes.data, 0, None,
+                                      C.byref(st) if st is not None else None))
+        return (out, st) if stats else out
+
+    def query_rays_device(self, rays_ptr: int, n: int, hits_ptr: int, *, stream=None, stats: bool = False):
+        """vx_query_rays on device arrays (e.g. torch tensors' data_ptr()): stream-ordered, no
+        synchronisation unless ``stats``."""
+        st = _abi.QueryStats() if stats else None
+        check(lib().vx_query_rays(self.handle, C.c_void_p(rays_ptr), int(n), C.c_void_p(hits_ptr), 1,
+                                  C.c_void_p(stream) if stream else None, C.byref(st) if st is not None else None))
+        return st
+
+    def pick(self, frame: Frame, px: int, py: int):
+        """What pixel (px, py) of ``frame`` shows: one HIT_DTYPE record (the pixel's view ray walked)."""
+        ray = np.zeros(1, RAY_DTYPE)
+        ray[0] = pixel_ray(frame, px, py)
+        return self.query_rays(ray)[0]
+
+    def place_views(self, u_matrix, cam_pos, places):
+        """drawOverlay with occlusion: (views, visible) for ``places`` (n x 3) -- the page's
+        projection (place_rays) and, per place, whether no opaque surface lies between the
+        camera and it (glass hides nothing)."""
+        views, rays = place_rays(u_matrix, cam_pos, places)
+        return views, hits_visible(self.query_rays(rays))
 
     def draw_scene(self, projection_matrix, position, sun, frame, time, *, width, height, mode_3d=True,
                    pixel_format=_abi.PIXEL_RGBA8):
