@@ -96,10 +96,21 @@ def field(built):
     return vx.field_build(scenes.small_proc(31, dims=(96, 64, 40), n_boxes=30, n_glass=5))
 
 
-@pytest.mark.parametrize("el,az,radius,n", SUNS)
-@pytest.mark.parametrize("max_steps", [0, 200])
-def test_field_doom_matches_numpy_restatement(field, el, az, radius, n, max_steps):
+# odd-shaped fields (scenes.odd_proc: blocks on the far faces): partial 8 x 8-cell blocks on
+# both axes, and X below one block, each for two plans of opposite signs on x and y
+ODD_FIELDS = {"odd37x29x11": (37, 29, 11), "odd5x43x9": (5, 43, 9)}
+_CASES = [pytest.param(None, m, *s, id="-".join(str(v) for v in (m,) + s)) for m in (0, 200) for s in SUNS] + \
+         [pytest.param(name, m, *s, id="-".join(str(v) for v in (name, m) + s))
+          for name in ODD_FIELDS for m in (0, 200) for s in (SUNS[0], SUNS[2])]
+
+
+@pytest.mark.parametrize("which,max_steps,el,az,radius,n", _CASES)
+def test_field_doom_matches_numpy_restatement(field, which, el, az, radius, n, max_steps):
     import oracle
+    if which is not None:
+        import voxmap_amd as vx
+        from voxmap_amd import scenes
+        field = vx.field_build(scenes.odd_proc(1, ODD_FIELDS[which]))
     d = oracle.sun_samples(_sun(el, az), radius, n)
     cone, _, kx, ky = oracle.exit_plan(d)
     assert cone

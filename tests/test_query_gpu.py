@@ -36,7 +36,14 @@ def _need_gpu(built):
 def _grid(name):
     from voxmap_amd import scenes
     return {"proc5": lambda: scenes.small_proc(5), "proc7": lambda: scenes.small_proc(7),
-            "glass_wall": scenes.glass_wall, "single_block": scenes.single_block}[name]()
+            "glass_wall": scenes.glass_wall, "single_block": scenes.single_block,
+            # an odd-shaped field with blocks on its far faces, at the default box cap and at cap 3 (the
+            # cap is also the copies' border: rays from outside the grid enter through it)
+            "odd": lambda: scenes.odd_proc(1, ODD_DIMS), "odd_cap3": lambda: scenes.odd_proc(1, ODD_DIMS)}[name]()
+
+
+ODD_DIMS = (37, 29, 11)
+DIST_CAP = {"odd_cap3": 3}           # vx_scene_desc.dist_cap per world; others: the default (64)
 
 
 # (camera above the grid, camera outside it looking in) as (sbj, rot) of the orbit camera
@@ -47,6 +54,8 @@ CAMS = {
     "single_block": [((20.0, 12.0, 12.0), (0.5, 0.0, 0.3)), ((-5.0, 12.0, 6.0), (1.45, 0.0, -math.pi / 2))],
 }
 SCENES = list(CAMS)
+CAMS["odd"] = CAMS["odd_cap3"] = [((18.5, 14.5, 11.2), (1.0, 0.0, 0.6)), ((-5.0, 14.0, 7.0), (1.45, 0.0, -math.pi / 2))]
+ODD_SCENES = ["odd", "odd_cap3"]
 
 
 class World:
@@ -63,8 +72,9 @@ class World:
         field = vx.field_build(self.grid)
         noise = np.zeros((4, 4, 4), np.uint8)
         self.scene = vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                              noise_format=vx.FORMAT_BIN, noise_size=(4, 4), dims=self.dims, device=0)
-        self.oracle = oracle.Oracle(self.scene.read_field(), noise)
+                              noise_format=vx.FORMAT_BIN, noise_size=(4, 4), dims=self.dims, device=0,
+                              dist_cap=DIST_CAP.get(name, 0))
+        self.oracle = oracle.Oracle(self.scene.read_field(), noise, cap=DIST_CAP.get(name, 64))
         self._params = vx.make_frame((X / 2, Y / 2, 10.0), (1.0, 0.0, 0.0), 64, 64).params
         self._cache = {}
 
@@ -200,7 +210,7 @@ def random_rays(w: World, n=2000, seed=1234):
 
 # ---- the cases ------------------------------------------------------------------
 
-@pytest.mark.parametrize("world", SCENES, indirect=True)
+@pytest.mark.parametrize("world", SCENES + ODD_SCENES, indirect=True)
 @pytest.mark.parametrize("cam", [0, 1])
 def test_pixel_rays_match_the_oracle(world, cam):
     fr, rays = world.pixel_rays(cam)
@@ -218,7 +228,7 @@ def test_pixel_rays_match_the_oracle(world, cam):
             assert ((ref["n"] == 1) & (ref["s"]["id"][:, 0] == 2)).any()     # glass with sky behind it
 
 
-@pytest.mark.parametrize("world", SCENES, indirect=True)
+@pytest.mark.parametrize("world", SCENES + ODD_SCENES, indirect=True)
 def test_random_rays_match_the_oracle(world):
     rays, kind = random_rays(world)
     assert len(rays) == 2000
@@ -386,7 +396,7 @@ def test_invalid_rays_are_answered_not_walked(world):
     _same(world.scene.query_rays(far), r_far, "far origins")
 
 
-@pytest.mark.parametrize("world", ["proc5", "glass_wall"], indirect=True)
+@pytest.mark.parametrize("world", ["proc5", "glass_wall"] + ODD_SCENES, indirect=True)
 def test_statistics_equal_the_oracles_counts(world):
     rays, _ = random_rays(world)
     _, px = world.pixel_rays(0)

@@ -1703,8 +1703,13 @@ __device__ __forceinline__ void shade_2d(const KernelArgs &a, float d0, float d1
 // blocks per CU, MI355X_MICROARCH.md "Residency"); every instantiation is held
 // to that budget explicitly (left alone the EXT ones take 66 VGPRs + 100 SGPRs
 // and run at 6 waves/SIMD).
+// The counting (STATS) instantiations are not timed and keep 13 more per-lane
+// counters live through every walk and march loop: at the 64-VGPR budget they
+// spilled 300-500 VGPRs, so they take the registers they need instead
+// (VX_OCC_WAVES(n): n waves/SIMD for the frames' kernels, no floor for STATS).
+#define VX_OCC_WAVES(n) amdgpu_waves_per_eu(STATS ? 1 : (n), STATS ? 8 : (n))
 #ifndef VX_OCC_ATTR
-#define VX_OCC_ATTR __attribute__((amdgpu_waves_per_eu(8, 8), amdgpu_num_sgpr(80)))
+#define VX_OCC_ATTR __attribute__((VX_OCC_WAVES(8), amdgpu_num_sgpr(80)))
 #endif
 // Workgroup = 256 threads = four 8x8-pixel waves side by side: a 32x8 pixel
 // block.  Each wave stores its own 8x8 tile (32-B row pieces): staging the

@@ -4,7 +4,7 @@
 // own: 5 waves/SIMD (96 VGPRs).  Their loop over a pixel's panes and mirror
 // walks spills heavily at the 8-wave budget of the other modes;
 // the template is the same text, so EXT 0-4 keep their code generation.
-#define VX_OCC_ATTR __attribute__((amdgpu_waves_per_eu(5, 5)))
+#define VX_OCC_ATTR __attribute__((VX_OCC_WAVES(5)))
 #include "vx_render.h"
 
 namespace vx {

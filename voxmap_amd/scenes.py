@@ -153,3 +153,69 @@ def glass_wall(dims=(64, 64, 16)) -> np.ndarray:
 def small_proc(seed: int, dims=(96, 48, 16), n_boxes=12, n_glass=3) -> np.ndarray:
     """A small S-proc-like scene that the scalar oracle renders in seconds."""
     return s_proc(seed, dims, n_boxes=n_boxes, n_glass=n_glass)
+
+
+def odd_proc(seed: int, dims, n_boxes: int = 10, n_glass: int = 6) -> np.ndarray:
+    """A scene for any X, Y, Z >= 1 (s_proc's ranges go empty below 9 x 9 x 5),
+    with blocks on the far faces of the grid, where a kernel's partial blocks
+    and mirrored coordinates end: ground at z = 0 (with holes and a second
+    colour when Z = 1, where nothing else can stand); boxes sized relative to
+    the dims, in turn flush with x = X - 1, with y = Y - 1, up to z = Z - 1 and
+    anywhere; a block column at (0, 0) and one at (X - 1, Y - 1) up to z = Z - 1;
+    when Z >= 5 overhang slabs over the four corners, the far one in the top
+    layer, with air beneath;
+    one-voxel glass panes, standing where Z >= 2, lying in the ground layer
+    where Z = 1.  Deterministic in ``seed``."""
+    X, Y, Z = (int(v) for v in dims)
+    assert X >= 1 and Y >= 1 and Z >= 1, dims
+    rng = np.random.default_rng(seed)
+    g = np.zeros((Z, Y, X), np.uint8)
+    g[0] = 2
+
+    def span(n, lo, hi):
+        """(start, length) of a run of lo..hi cells (clipped to n) inside [0, n)."""
+        length = int(rng.integers(min(lo, n), min(hi, n) + 1))
+        return int(rng.integers(0, n - length + 1)), length
+
+    if Z == 1:
+        # the top of a one-layer field is the grid's face, which shows nothing:
+        # what a frame sees are the walls of the holes
+        for k in range(max(6, X * Y // 8)):
+            x0, w = span(X, 1, max(1, X // 12))
+            y0, d = span(Y, 1, max(1, Y // 12))
+            g[0, y0:y0 + d, x0:x0 + w] = 13 if k % 3 == 0 else 0
+    else:
+        for k in range(n_boxes):
+            x0, w = span(X, 1, max(2, X // 4))
+            y0, d = span(Y, 1, max(2, Y // 4))
+            hgt = int(rng.integers(1, Z))              # 1 .. Z - 1 layers above the ground
+            col = int(rng.integers(1, 21))
+            if k % 4 == 0:
+                x0 = X - w
+            elif k % 4 == 1:
+                y0 = Y - d
+            elif k % 4 == 2:
+                hgt = Z - 1
+            g[1:1 + hgt, y0:y0 + d, x0:x0 + w] = col
+    if Z >= 5:
+        # overhang slabs over the four corners, air beneath: a sun of either sign on x and on
+        # y finds cells whose rays all end in a slab (what a doom table marks) next to the grid
+        # face its coordinates are mirrored from; the far one in the top layer, each wide
+        # enough for a sun slope of about 1
+        w, d = max(4, X // 3), max(4, Y // 3)
+        for far_x, far_y, z in ((1, 1, Z - 1), (0, 1, Z - 2), (1, 0, Z - 3), (0, 0, Z - 2)):
+            xs = slice(max(0, X - w), X) if far_x else slice(0, w)
+            ys = slice(max(0, Y - d), Y) if far_y else slice(0, d)
+            g[z, ys, xs] = int(rng.integers(1, 21))
+    for k in range(n_glass):
+        x0, lx = span(X, 1, max(2, X // 3))
+        y0, ly = span(Y, 1, max(2, Y // 3))
+        hgt = int(rng.integers(1, Z)) if Z >= 2 else 0
+        z0, z1 = (1, 1 + hgt) if Z >= 2 else (0, 1)
+        if k % 2 == 0:
+            g[z0:z1, y0, x0:x0 + lx] = GLASS
+        else:
+            g[z0:z1, y0:y0 + ly, x0] = GLASS
+    g[:, 0, 0] = 7
+    g[:, Y - 1, X - 1] = 9
+    return g
