@@ -59,18 +59,7 @@ __global__ __launch_bounds__(kWG) void k_query(const QueryArgs a) {
             // iv = RN(1/d), +inf for d = 0 (a positive axis, as -0 is): rcp_ranged where
             // the whole wave is in its range, the IEEE division otherwise
             float iv0, iv1, iv2;
-            {
-                const unsigned lo_b = 0x2B800000u, span = 0x54000000u - 0x2B800000u;   // 2^-40, 2^41
-                const bool ok = (__float_as_uint(fabsf(d0)) - lo_b) < span && (__float_as_uint(fabsf(d1)) - lo_b) < span &&
-                                (__float_as_uint(fabsf(d2)) - lo_b) < span;
-                if (__builtin_expect(__ballot(!ok) == 0, 1)) {
-                    iv0 = rcp_ranged(d0); iv1 = rcp_ranged(d1); iv2 = rcp_ranged(d2);
-                } else {
-                    iv0 = d0 != 0.0f ? 1.0f / d0 : kInf;
-                    iv1 = d1 != 0.0f ? 1.0f / d1 : kInf;
-                    iv2 = d2 != 0.0f ? 1.0f / d2 : kInf;
-                }
-            }
+            ray_rcp(d0, d1, d2, iv0, iv1, iv2);
             // grid slabs from the ray's own origin; a zero component misses unless
             // the origin lies inside that slab
             float tlo = 0.0f, thi = kInf;

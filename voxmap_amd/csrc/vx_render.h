@@ -286,27 +286,8 @@ __device__ __forceinline__ unsigned lin_index(const KernelArgs &a, int x, int y,
 // (sky, safe == 0 or the step budget); cells kept as exact fp32 integers; the
 // three-way min and its tie test as min3/med3 (two or more axes share the
 // minimum iff med3 == min3, then the literal length of render.frag:105-116).
-__device__ __forceinline__ float march_len(const SunRay &S, float f0, float f1, float f2) {
-    const float x0 = -f0 * S.sign[0], x1 = -f1 * S.sign[1], x2 = -f2 * S.sign[2];     // :94
-    const float d0 = (x0 - floorf(x0)) + 1e-4f;
-    const float d1 = (x1 - floorf(x1)) + 1e-4f;
-    const float d2 = (x2 - floorf(x2)) + 1e-4f;
-    const float t0 = div_const(d0, S.abs[0], S.rcp[0]);                                // :97
-    const float t1 = div_const(d1, S.abs[1], S.rcp[1]);
-    const float t2 = div_const(d2, S.abs[2], S.rcp[2]);
-    float len = __builtin_fminf(__builtin_fminf(t0, t1), t2);                         // :100-105, one axis
-    if (__builtin_amdgcn_fmed3f(t0, t1, t2) == len) {                                  // ties: literal length
-        const float v0 = t0 == len ? t0 : 0.0f, v1 = t1 == len ? t1 : 0.0f, v2 = t2 == len ? t2 : 0.0f;
-        len = sqrtf(v0 * v0 + v1 * v1 + v2 * v2);
-    }
-    return len;
-}
-
-// march_len with the sun's axis signs known at compile time (SG bit i: r_i > 0;
-// the fast paths have no zero component): fract(-f*s) + 1e-4 without the
-// multiply -- for s > 0 it is (-f) - floor(-f) = ceil(f) - f, the same single
-// IEEE subtraction (floor(-f) = -ceil(f)); for s < 0, f - floor(f).
-// the step length from the distance terms d_i = fract(-f_i*s_i) + 1e-4 (:94-105)
+// the step length from the distance terms d_i = fract(-f_i*s_i) + 1e-4 (:94-116):
+// the one place that holds the quotients, the minimum and the tie rule
 __device__ __forceinline__ float march_len_d(const SunRay &S, float d0, float d1, float d2) {
     const float t0 = div_const(d0, S.abs[0], S.rcp[0]);                                // :97
     const float t1 = div_const(d1, S.abs[1], S.rcp[1]);
@@ -319,20 +300,28 @@ __device__ __forceinline__ float march_len_d(const SunRay &S, float d0, float d1
     return len;
 }
 
+__device__ __forceinline__ float march_len(const SunRay &S, float f0, float f1, float f2) {
+    const float x0 = -f0 * S.sign[0], x1 = -f1 * S.sign[1], x2 = -f2 * S.sign[2];     // :94
+    return march_len_d(S, (x0 - floorf(x0)) + 1e-4f, (x1 - floorf(x1)) + 1e-4f, (x2 - floorf(x2)) + 1e-4f);
+}
+
+// The distance terms with the sun's axis signs known at compile time (SG bit i:
+// r_i > 0; the fast paths have no zero component): fract(-f*s) + 1e-4 without
+// the multiply -- for s > 0 it is (-f) - floor(-f) = ceil(f) - f, the same single
+// IEEE subtraction (floor(-f) = -ceil(f)); for s < 0, f - floor(f).
+template <int SG>
+__device__ __forceinline__ void march_terms_sg(float f0, float f1, float f2, float &d0, float &d1, float &d2) {
+    d0 = ((SG & 1) ? ceilf(f0) - f0 : f0 - floorf(f0)) + 1e-4f;
+    d1 = ((SG & 2) ? ceilf(f1) - f1 : f1 - floorf(f1)) + 1e-4f;
+    d2 = ((SG & 4) ? ceilf(f2) - f2 : f2 - floorf(f2)) + 1e-4f;
+}
+
+// march_len with those terms
 template <int SG>
 __device__ __forceinline__ float march_len_sg(const SunRay &S, float f0, float f1, float f2) {
-    const float d0 = ((SG & 1) ? ceilf(f0) - f0 : f0 - floorf(f0)) + 1e-4f;
-    const float d1 = ((SG & 2) ? ceilf(f1) - f1 : f1 - floorf(f1)) + 1e-4f;
-    const float d2 = ((SG & 4) ? ceilf(f2) - f2 : f2 - floorf(f2)) + 1e-4f;
-    const float t0 = div_const(d0, S.abs[0], S.rcp[0]);                                // :97
-    const float t1 = div_const(d1, S.abs[1], S.rcp[1]);
-    const float t2 = div_const(d2, S.abs[2], S.rcp[2]);
-    float len = __builtin_fminf(__builtin_fminf(t0, t1), t2);                         // :100-105, one axis
-    if (__builtin_amdgcn_fmed3f(t0, t1, t2) == len) {                                  // ties: literal length
-        const float v0 = t0 == len ? t0 : 0.0f, v1 = t1 == len ? t1 : 0.0f, v2 = t2 == len ? t2 : 0.0f;
-        len = sqrtf(v0 * v0 + v1 * v1 + v2 * v2);
-    }
-    return len;
+    float d0, d1, d2;
+    march_terms_sg<SG>(f0, f1, f2, d0, d1, d2);
+    return march_len_d(S, d0, d1, d2);
 }
 
 // march_len_sg inside the march loop, where every f_i is a step's
@@ -351,18 +340,9 @@ __device__ __forceinline__ float march_len_sg(const SunRay &S, float f0, float f
 // negative (the hit point's rounding), so march_pad keeps march_len_sg there.
 template <int SG>
 __device__ __forceinline__ float march_len_fract(const SunRay &S, float f0, float f1, float f2) {
-    const float d0 = __builtin_amdgcn_fractf((SG & 1) ? -f0 : f0) + 1e-4f;
-    const float d1 = __builtin_amdgcn_fractf((SG & 2) ? -f1 : f1) + 1e-4f;
-    const float d2 = __builtin_amdgcn_fractf((SG & 4) ? -f2 : f2) + 1e-4f;
-    const float t0 = div_const(d0, S.abs[0], S.rcp[0]);                                // :97
-    const float t1 = div_const(d1, S.abs[1], S.rcp[1]);
-    const float t2 = div_const(d2, S.abs[2], S.rcp[2]);
-    float len = __builtin_fminf(__builtin_fminf(t0, t1), t2);                         // :100-105, one axis
-    if (__builtin_amdgcn_fmed3f(t0, t1, t2) == len) {                                  // ties: literal length
-        const float v0 = t0 == len ? t0 : 0.0f, v1 = t1 == len ? t1 : 0.0f, v2 = t2 == len ? t2 : 0.0f;
-        len = sqrtf(v0 * v0 + v1 * v1 + v2 * v2);
-    }
-    return len;
+    return march_len_d(S, __builtin_amdgcn_fractf((SG & 1) ? -f0 : f0) + 1e-4f,
+                       __builtin_amdgcn_fractf((SG & 2) ? -f1 : f1) + 1e-4f,
+                       __builtin_amdgcn_fractf((SG & 4) ? -f2 : f2) + 1e-4f);
 }
 
 __device__ __forceinline__ bool march_fast(const KernelArgs &a, const SunRay &S, const uint8_t *sun, float c0, float c1, float c2, float f0,
@@ -533,9 +513,8 @@ __device__ __forceinline__ int march_soft(const KernelArgs &a, const int8_t *sun
     const float exy = __builtin_fmaf(c1 + a.SBf, xpf, (c0 + a.SBf) + kBias);
     const float e2 = (c2 + a.SBf) + kBias;
     const u32x4 rsrc = buf_rsrc(sun - 0x4B000000, kRsrcS8);
-    const float d0 = ((SG & 1) ? ceilf(f0) - f0 : f0 - floorf(f0)) + 1e-4f;     // march_len_sg's terms
-    const float d1 = ((SG & 2) ? ceilf(f1) - f1 : f1 - floorf(f1)) + 1e-4f;
-    const float d2 = ((SG & 4) ? ceilf(f2) - f2 : f2 - floorf(f2)) + 1e-4f;
+    float d0, d1, d2;
+    march_terms_sg<SG>(f0, f1, f2, d0, d1, d2);
     int lit = 0;
     for (int k = 0; k < F.n_sun; k++) {
         cnt.shadow_rays++;
@@ -602,6 +581,11 @@ __device__ __forceinline__ bool march_brick(const KernelArgs &a, const SunRay &S
     // (render.frag:234: a block on the last step still ends with step == MAX_STEPS);
     // a block found earlier ends the loop with step + 1 < maxs
     return tv != 0 || step + 1 >= maxs;
+}
+
+// the sign pattern of a fast-path sun ray (bit i: r_i > 0)
+__device__ __forceinline__ int sun_sg(const SunRay &S) {
+    return (S.sign[0] > 0.0f ? 1 : 0) | (S.sign[1] > 0.0f ? 2 : 0) | (S.sign[2] > 0.0f ? 4 : 0);
 }
 
 // Literal path for any other sun direction (zero or tiny components: the
@@ -691,7 +675,7 @@ __device__ __forceinline__ bool march_sun(const KernelArgs &a, const SunRay S, f
                                           float f1, float f2, Counters &cnt) {
     if (S.fast && a.sunp) {
         // wave-uniform switch on the frame's sun signs: one specialised loop each
-        const int sg = (S.sign[0] > 0.0f ? 1 : 0) | (S.sign[1] > 0.0f ? 2 : 0) | (S.sign[2] > 0.0f ? 4 : 0);
+        const int sg = sun_sg(S);
         // the frame's cone copy, else the octant's orthant copy, else the plain channel
         const int8_t *ch = a.sunc ? a.sunc
                          : a.sunx ? a.sunx + (size_t)sg * a.sunp_texels : S.up ? a.sunp : a.sunp + a.sunp_texels;
@@ -708,6 +692,13 @@ __device__ __forceinline__ bool march_sun(const KernelArgs &a, const SunRay S, f
                   : march_literal(a, S, ch, c0, c1, c2, f0, f1, f2, cnt);
 }
 
+// a quad's in-face offsets (lo along u = (ax+1)%3, hi along v = (ax+2)%3) per axis
+__device__ __forceinline__ void uv_offsets(int ax, float lo, float hi, float &o0, float &o1, float &o2) {
+    o0 = ax == 2 ? lo : (ax == 1 ? hi : 0.0f);
+    o1 = ax == 0 ? lo : (ax == 2 ? hi : 0.0f);
+    o2 = ax == 1 ? lo : (ax == 0 ? hi : 0.0f);
+}
+
 // The offset (per axis, as exact fp32 integers) of the face with normal index
 // nidx of cell (x, y, z) from the origin of the greedy quad covering it
 // (a.qface: du along u = (ax+1)%3, dv along v = (ax+2)%3, 0 on the face axis);
@@ -717,20 +708,31 @@ __device__ __forceinline__ void quad_offsets(const KernelArgs &a, int ax, int ni
                                              float &o1, float &o2) {
     unsigned q = a.qface[(size_t)nidx * a.XYZ + lin_index(a, x, y, z)];
     q = q == 0xFFFFu ? 0u : q;
-    const float lo = (float)(q & 0xffu), hi = (float)(q >> 8);
-    o0 = ax == 2 ? lo : (ax == 1 ? hi : 0.0f);
-    o1 = ax == 0 ? lo : (ax == 2 ? hi : 0.0f);
-    o2 = ax == 1 ? lo : (ax == 0 ? hi : 0.0f);
+    uv_offsets(ax, (float)(q & 0xffu), (float)(q >> 8), o0, o1, o2);
 }
 
 // The same offsets from a qcopy word (the octant's entry faces, 10 bits per
 // face axis ax: du | dv << 5, launch_qcopy) -- chunks of at most 32 cells.
 __device__ __forceinline__ void qcopy_offsets(uint32_t w, int ax, float &o0, float &o1, float &o2) {
     const unsigned q = (w >> (10 * ax)) & 0x3ffu;
-    const float lo = (float)(q & 31u), hi = (float)(q >> 5);
-    o0 = ax == 2 ? lo : (ax == 1 ? hi : 0.0f);
-    o1 = ax == 0 ? lo : (ax == 2 ? hi : 0.0f);
-    o2 = ax == 1 ? lo : (ax == 0 ? hi : 0.0f);
+    uv_offsets(ax, (float)(q & 31u), (float)(q >> 5), o0, o1, o2);
+}
+
+// iv = RN(1/d) (kInf for d = 0, a positive axis as -0 is) of a walk outside
+// primary(), which fuses its slab products into the fast branch: rcp_ranged is
+// exact for |d| in [2^-40, 2^41) -- every lane of nearly every wave; a wave with
+// a lane outside it (a zero or tiny component) takes the IEEE division.
+__device__ __forceinline__ void ray_rcp(float d0, float d1, float d2, float &iv0, float &iv1, float &iv2) {
+    const unsigned lo_b = 0x2B800000u, span = 0x54000000u - 0x2B800000u;   // 2^-40, 2^41
+    const bool ok = (__float_as_uint(fabsf(d0)) - lo_b) < span && (__float_as_uint(fabsf(d1)) - lo_b) < span &&
+                    (__float_as_uint(fabsf(d2)) - lo_b) < span;
+    if (__builtin_expect(__ballot(!ok) == 0, 1)) {
+        iv0 = rcp_ranged(d0); iv1 = rcp_ranged(d1); iv2 = rcp_ranged(d2);
+    } else {
+        iv0 = d0 != 0.0f ? 1.0f / d0 : kInf;
+        iv1 = d1 != 0.0f ? 1.0f / d1 : kInf;
+        iv2 = d2 != 0.0f ? 1.0f / d2 : kInf;
+    }
 }
 
 // ---------------- primary visibility ----------------
@@ -994,8 +996,10 @@ __device__ __forceinline__ unsigned long long face_key(const KernelArgs &a, int 
             (unsigned long long)(ov - kv * CH)) * S + (unsigned long long)(ou - ku * CH);
 }
 
-// One pass over the view ray's glass faces (the walk of primary visibility,
-// scalar form like walk_reflect; oracle walk() with glass_layer 3): of the
+// One pass over the view ray's glass faces (the walk of primary visibility in
+// the oracle's integer form, not the fp32 step of primary / walk_reflect: a cold
+// path compiled into every timed kernel, whose register footprint sets EXT 0's
+// scratch size; oracle walk() with glass_layer 3): of the
 // front-facing glass entries before the first opaque entry, the one drawn
 // first after key `klast` (none: have_last false) among those nearer than
 // tmax.  Returns false if there is none; else its G-buffer record
@@ -1366,8 +1370,7 @@ __device__ __forceinline__ void shade_block(const KernelArgs &a, const Surf &g, 
     if (shadeFactor > 0.0f && !(F.flags & VX_FLAG_NO_SHADOW)) {                        // :232-235
         // the exit copy every sample reads (sunc, or the octant's orthant copy
         // when they share one sign pattern): a first step into a marked block is lit
-        const int sg0 = (F.sun_k[0].sign[0] > 0.0f ? 1 : 0) | (F.sun_k[0].sign[1] > 0.0f ? 2 : 0) |
-                        (F.sun_k[0].sign[2] > 0.0f ? 4 : 0);
+        const int sg0 = sun_sg(F.sun_k[0]);
         const int8_t *xch = EXT != 2 || !a.sunp || !F.sun_k[0].fast ? nullptr
                           : a.sunc ? a.sunc
                           : a.sunx && F.soft_sg >= 0 ? a.sunx + (size_t)sg0 * a.sunp_texels : nullptr;
@@ -1446,18 +1449,7 @@ __device__ __forceinline__ int walk_reflect(const KernelArgs &a, int B0, int B1,
     const int oct = (d0 < 0.0f ? 1 : 0) | (d1 < 0.0f ? 2 : 0) | (d2 < 0.0f ? 4 : 0);
     const uint32_t *pp = a.prim + (size_t)oct * a.copy_texels;
     float iv0, iv1, iv2;
-    {
-        const unsigned lo_b = 0x2B800000u, span = 0x54000000u - 0x2B800000u;   // 2^-40, 2^41
-        const bool ok = (__float_as_uint(fabsf(d0)) - lo_b) < span && (__float_as_uint(fabsf(d1)) - lo_b) < span &&
-                        (__float_as_uint(fabsf(d2)) - lo_b) < span;
-        if (__builtin_expect(__ballot(!ok) == 0, 1)) {
-            iv0 = rcp_ranged(d0); iv1 = rcp_ranged(d1); iv2 = rcp_ranged(d2);
-        } else {
-            iv0 = d0 != 0.0f ? 1.0f / d0 : kInf;
-            iv1 = d1 != 0.0f ? 1.0f / d1 : kInf;
-            iv2 = d2 != 0.0f ? 1.0f / d2 : kInf;
-        }
-    }
+    ray_rcp(d0, d1, d2, iv0, iv1, iv2);
     const bool p0 = !(d0 < 0.0f), p1 = !(d1 < 0.0f), p2 = !(d2 < 0.0f);
     const float s0 = p0 ? 1.0f : -1.0f, s1 = p1 ? 1.0f : -1.0f, s2 = p2 ? 1.0f : -1.0f;
     const float hp0 = p0 ? 1.0f : 0.0f, hp1 = p1 ? 1.0f : 0.0f, hp2 = p2 ? 1.0f : 0.0f;
