@@ -874,6 +874,9 @@ static void reflect_color(const shade_ctx *c, const vxo_gbuf *gl, const float rd
     const int a = gl->normal_idx >> 1;
     float R[3] = {rd[0], rd[1], rd[2]};
     R[a] = -R[a];
+    /* a direction that is not finite (a hit at t = 0: rayDir = normalize(0) = NaN) is not walked: the ray is
+     * counted and is the sky along it with no fetch, like a start outside the grid */
+    const int finite = fabsf(R[0]) < INFINITY && fabsf(R[1]) < INFINITY && fabsf(R[2]) < INFINITY;
     int B[3], c0[3];
     float o[3];
     for (int i = 0; i < 3; i++) {
@@ -890,7 +893,7 @@ static void reflect_color(const shade_ctx *c, const vxo_gbuf *gl, const float rd
     }
     vxo_gbuf h[2];
     int fetches = 0, cap_hit = 0;
-    const int n = walk(c->s, B, o, R, c0, 0, h, &fetches, &cap_hit, NULL, 0, NULL);
+    const int n = finite ? walk(c->s, B, o, R, c0, 0, h, &fetches, &cap_hit, NULL, 0, NULL) : 0;
     if (st) { st->reflect_rays++; st->reflect_fetches += (uint64_t)fetches; st->primary_cap_hits += (uint64_t)cap_hit; }
     float rgba[4];
     if (n == 0) {

@@ -150,10 +150,12 @@ int vx::check_frame(const vx_frame_params *p, int w, int h, int fmt) {
     if (!p) return set_error(VX_EINVAL, "null scene/params");
     if (w <= 0 || h <= 0 || w > 32768 || h > 32768) return set_error(VX_EINVAL, "frame size out of range");
     if (fmt != VX_PIXEL_RGBA32F && fmt != VX_PIXEL_RGBA8) return set_error(VX_EINVAL, "unknown pixel format");
-    for (int i = 0; i < 3; i++)
-        if (!std::isfinite(p->cam_fract[i]) || !std::isfinite(p->ray_fwd[i]) || !std::isfinite(p->ray_right[i]) ||
-            !std::isfinite(p->ray_up[i]) || !std::isfinite(p->sun_dir[i]))
-            return set_error(VX_EINVAL, "non-finite frame parameter");
+    const struct { const char *name; const float *v; } vec[] = {
+        {"cam_fract", p->cam_fract}, {"ray_fwd", p->ray_fwd}, {"ray_right", p->ray_right}, {"ray_up", p->ray_up},
+        {"sun_dir", p->sun_dir}};
+    for (const auto &f : vec)
+        for (int i = 0; i < 3; i++)
+            if (!std::isfinite(f.v[i])) return set_error(VX_EINVAL, std::string("non-finite frame parameter ") + f.name);
     // u_fractPos is fract(position) (render.js:289-290); the primary traversal
     // relies on 0 <= o < 1 and on camera-relative cells below 2^22
     for (int i = 0; i < 3; i++) {

@@ -1465,7 +1465,10 @@ __device__ __forceinline__ int walk_reflect(const KernelArgs &a, int B0, int B1,
         return pp[xy + __umul24(__float_as_uint(h2 + bz), a.XpYp)];
     };
     uint32_t t = fetch();
-    if (t >= kSentinel) return 0;
+    // a direction that is not finite (a hit at t = 0: rayDir = normalize(0) = NaN) is not walked: sky
+    // along it with no fetch counted, like a start outside the grid (oracle reflect_color())
+    const bool finite = fabsf(d0) < kInf && fabsf(d1) < kInf && fabsf(d2) < kInf;
+    if (t >= kSentinel || !finite) return 0;
     cnt.refl_fetch++;
     int prev = t & 0xff;
     float E0 = cvt_f32_ubyte1(t), E1 = cvt_f32_ubyte2(t), E2 = cvt_f32_ubyte3(t);
