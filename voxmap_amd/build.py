@@ -19,7 +19,7 @@ OUT = os.path.join(HERE, "libvoxmap_hip.so")
 SOURCES = ["vx_render_e56.hip", "vx_render_e2.hip", "vx_render_e1.hip", "vx_render_e0.hip", "vx_render_e3.hip",
            "vx_render_e4.hip", "vx_kernels.hip", "vx_field_gpu.hip", "vx_query.hip", "vx_api.cpp", "vx_host.cpp",
            "vx_codec.cpp", "vx_field.cpp", "vx_frame.cpp", "vx_mgpu.cpp"]
-HEADERS = ["vx_internal.h", "vx_render.h"]
+HEADERS = ["vx_internal.h", "vx_render.h", "vx_device.h"]
 ARCH = os.environ.get("VOXMAP_ARCH", "gfx950")
 # -fno-slp-vectorize: packed FP32 (v_pk_*) issues at the cost of two scalar ops
 # on gfx950 (profiles/r01_valu_costs.txt), so SLP packing only adds moves.
