@@ -76,8 +76,34 @@ void sun_samples(const float sun[3], float radius, int n, float out[][3]) {
     }
 }
 
+// FrameConsts::rays_ranged: whether every view ray d = fwd + nx*right + ny*up
+// with |nx|, |ny| <= 1, as the kernel rounds it in fp32, has |d|^2 in
+// [2^-80, 2^82), the domain of normalize3_ranged.  A sufficient test on the
+// basis alone, in double; when in doubt, no.
+//   above: |d| <= S = |fwd| + |right| + |up|, and S < 2^40;
+//   below: every d ends on the plane through fwd spanned by right and up, so
+//          |d| >= dist = |fwd . n| / |n|, n = right x up, the distance of
+//          that plane from the origin (the centre ray's length for an orthogonal
+//          basis); asked: dist >= S * 2^-10 and S >= 2^-28, so |d| >= 2^-38.
+// The fp32 evaluation of d moves each component by less than S * 2^-22 (two
+// products and two sums of terms <= S, each rounded once; none underflows, the
+// result being >= 2^-38 in length), far below dist, and the three squares and
+// their sum round by 2^-22 relative at the most.
+static int rays_ranged(const vx_frame_params &p) {
+    const double f[3] = {p.ray_fwd[0], p.ray_fwd[1], p.ray_fwd[2]};
+    const double r[3] = {p.ray_right[0], p.ray_right[1], p.ray_right[2]};
+    const double u[3] = {p.ray_up[0], p.ray_up[1], p.ray_up[2]};
+    auto len = [](const double v[3]) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
+    const double n[3] = {r[1] * u[2] - r[2] * u[1], r[2] * u[0] - r[0] * u[2], r[0] * u[1] - r[1] * u[0]};
+    const double S = len(f) + len(r) + len(u), ln = len(n);
+    if (!(ln > 0.0) || !(S < 0x1p40) || !(S >= 0x1p-28)) return 0;
+    const double dist = std::fabs(f[0] * n[0] + f[1] * n[1] + f[2] * n[2]) / ln;
+    return dist >= S * 0x1p-10 ? 1 : 0;
+}
+
 void frame_consts(const vx_frame_params &p, int w, int h, int X, int Y, int Z, int max_steps, FrameConsts &fc) {
     std::memset(&fc, 0, sizeof fc);
+    fc.rays_ranged = rays_ranged(p);
     for (int i = 0; i < 3; i++) {
         fc.cam_cell[i] = p.cam_cell[i];
         fc.cam_fract[i] = p.cam_fract[i];

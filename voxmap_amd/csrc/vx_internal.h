@@ -48,6 +48,8 @@ struct FrameConsts {
     float slab_lo[3], slab_hi[3], cell_lo[3], cell_hi[3];
     float fwd[3], right[3], up[3];
     float fw, fh, rcp_w, rcp_h;        // (float)w, (float)h and RN(1/w), RN(1/h)
+    int rays_ranged;                   // 1: every view ray fwd + nx*right + ny*up (|nx|, |ny| <= 1) has its
+                                       // length in [2^-40, 2^41) (normalize3_ranged's domain); 0: not known
     float sun[3];                      // u_sunDir
     float sun_sign[3];                 // sign(u_sunDir) (render.frag:94)
     float sun_abs[3], sun_rcp[3];      // |u_sunDir|, RN(1/|u_sunDir|)

@@ -23,7 +23,11 @@
 //   * length(m*t) with a single selected axis -> t (sqrt(RN(t*t)) == t);
 //   * unorm8 decode b/255 -> typed UNORM buffer loads (the texture data unit
 //     returns RN(b/255) for every byte, tools/micro/unorm_check.hip);
-//   * per-frame uniform-only expressions -> host (vx_frame.cpp).
+//   * per-frame uniform-only expressions -> host (vx_frame.cpp);
+//   * min / max / clamp as v_min / v_max / the clamp modifier, and sqrtf /
+//     normalize without their range handling, where the operands are proven
+//     (fmin_fin, fmax_fin, clamp01, sqrt_ranged, normalize3_ranged; the view
+//     rays' lengths by a per-frame bit from the host, FrameConsts::rays_ranged).
 // Rejected experiments (bricked layouts, LDS r*k tables, hand-batched sky
 // loads, typed primary loads, ...) are measured in profiles/ and kept in git
 // history, not here.
@@ -48,6 +52,21 @@ __device__ __forceinline__ float gmin(float x, float y) { return y < x ? y : x; 
 __device__ __forceinline__ float gmax(float x, float y) { return x < y ? y : x; }
 __device__ __forceinline__ float gclamp(float x, float a, float b) { return gmin(gmax(x, a), b); }
 __device__ __forceinline__ float gmix(float x, float y, float a) { return x * (1.0f - a) + y * a; }
+// The proven forms: one v_min_f32 / v_max_f32, or the result clamp of the op
+// that produces x, where gmin / gmax / gclamp are a v_cmp + v_cndmask pair
+// each.  The selects and the hardware ops differ only on a NaN operand (the
+// select returns its first argument, the hardware the other one) and in the
+// sign of a zero result when the operands are zeros of both signs, so
+//   fmin_fin, fmax_fin: neither operand is NaN, and they are not +0 and -0;
+//   clamp01: x is not NaN and not -0 -- or the value is only packed into a
+//            byte (pack_rgba8), which takes NaN and both zeros to 0 either way.
+// Each call site states why its operands qualify; tools/micro/clamp_check.hip
+// runs both forms over every float (profiles/r07_clamp_check.txt).  The
+// clamp of a NaN is 0 by DX10_CLAMP, which every kernel here has set
+// (kernel_meta.check reads the kernel descriptors).
+__device__ __forceinline__ float fmin_fin(float x, float y) { return __builtin_fminf(x, y); }
+__device__ __forceinline__ float fmax_fin(float x, float y) { return __builtin_fmaxf(x, y); }
+__device__ __forceinline__ float clamp01(float x) { return __builtin_amdgcn_fmed3f(x, 0.0f, 1.0f); }
 // ivec(float) of the contract: NaN -> 0, saturate at +-2^24 (branch-free)
 __device__ __forceinline__ int f2i(float x) {
     const float c = __builtin_fminf(__builtin_fmaxf(x, -16777216.0f), 16777216.0f);
@@ -949,18 +968,34 @@ __device__ __forceinline__ int primary(const KernelArgs &a, int oct, float d0, f
         nrec = 1;
     }
     if (hit) {
-        Surf &h = gl ? g1 : g0;
         const float upf = hpos ? 0.0f : 1.0f;
         const float r0 = hr0 - hq0, r1 = hr1 - hq1, r2 = hr2 - hq2;
-        h.id = col == kGlass ? 2 : 0;
-        h.color = (int)col;
-        h.nidx = 2 * hax + (hpos ? 1 : 0);
-        h.c0 = (r0 + F.cam_cell_f[0]) + (hax == 0 ? upf : 0.0f);
-        h.c1 = (r1 + F.cam_cell_f[1]) + (hax == 1 ? upf : 0.0f);
-        h.c2 = (r2 + F.cam_cell_f[2]) + (hax == 2 ? upf : 0.0f);
-        h.f0 = hax == 0 ? 0.0f : (o0 + te * d0) - r0;
-        h.f1 = hax == 1 ? 0.0f : (o1 + te * d1) - r1;
-        h.f2 = hax == 2 ? 0.0f : (o2 + te * d2) - r2;
+        const int id = col == kGlass ? 2 : 0;
+        const int nidx = 2 * hax + (hpos ? 1 : 0);
+        const float c0 = (r0 + F.cam_cell_f[0]) + (hax == 0 ? upf : 0.0f);
+        const float c1 = (r1 + F.cam_cell_f[1]) + (hax == 1 ? upf : 0.0f);
+        const float c2 = (r2 + F.cam_cell_f[2]) + (hax == 2 ? upf : 0.0f);
+        const float f0 = hax == 0 ? 0.0f : (o0 + te * d0) - r0;
+        const float f1 = hax == 1 ? 0.0f : (o1 + te * d1) - r1;
+        const float f2 = hax == 2 ? 0.0f : (o2 + te * d2) - r2;
+        // The record goes behind a glass record if the lane has one.  A wave
+        // without any (nearly all: glass is 0.2 % of the headline frame's pixels)
+        // writes g0 with no select per field; in the others every lane writes
+        // g1, which only a lane with a glass record reads, and a lane without
+        // one also g0.  (Values selected, never the reference: stores through a
+        // selected reference keep both records in scratch.)
+        if (__builtin_expect(__ballot(gl) == 0, 1)) {
+            g0.id = id; g0.color = (int)col; g0.nidx = nidx;
+            g0.c0 = c0; g0.c1 = c1; g0.c2 = c2;
+            g0.f0 = f0; g0.f1 = f1; g0.f2 = f2;
+        } else {
+            g1.id = id; g1.color = (int)col; g1.nidx = nidx;
+            g1.c0 = c0; g1.c1 = c1; g1.c2 = c2;
+            g1.f0 = f0; g1.f1 = f1; g1.f2 = f2;
+            g0.id = gl ? g0.id : id; g0.color = gl ? g0.color : (int)col; g0.nidx = gl ? g0.nidx : nidx;
+            g0.c0 = gl ? g0.c0 : c0; g0.c1 = gl ? g0.c1 : c1; g0.c2 = gl ? g0.c2 : c2;
+            g0.f0 = gl ? g0.f0 : f0; g0.f1 = gl ? g0.f1 : f1; g0.f2 = gl ? g0.f2 : f2;
+        }
         nrec++;
     }
     t_hit = te;
@@ -1163,7 +1198,10 @@ __device__ __forceinline__ float sdf_lin(const KernelArgs &a, float c0, float c1
         const float w1 = gmix(v10, v11, wy);
         res[ch] = gmix(w0, w1, wz) * 255.0f;
     }
-    return gmin(res[0], res[1]);
+    // fmin_fin: each res is a chain of lerps of texels k/255 with weights in
+    // [0, 1], times 255 -- finite, and >= +0 (products and sums of values >= +0
+    // are never -0)
+    return fmin_fin(res[0], res[1]);
 }
 
 // REPEAT wrap of an integer-valued float onto [0, n), n a power of two:
@@ -1213,11 +1251,15 @@ __device__ __forceinline__ void normalize3(float v0, float v1, float v2, float &
 }
 
 // ---------------- render.frag main(), sky branch (render.frag:148-205) ----------------
-__device__ __forceinline__ void shade_sky(const KernelArgs &a, float d0, float d1, float d2, float o[4],
-                          Counters &cnt) {
-    const FrameConsts &F = a.fc;
-    float r0, r1, r2;
-    normalize3(d0, d1, d2, r0, r1, r2);          // skybox modelled at infinity
+// The sky's ray direction and clear-sky colour (render.frag:152-176).  RANGED:
+// the length of d is known to lie in [2^-40, 2^41) (a view ray of a frame
+// whose FrameConsts::rays_ranged is set), so normalize3_ranged is the IEEE
+// result and r is finite, |r_i| <= 1.
+template <bool RANGED>
+__device__ __forceinline__ void sky_clear(const FrameConsts &F, float d0, float d1, float d2, float &r0, float &r1,
+                                          float &r2, float sky[3]) {
+    if (RANGED) normalize3_ranged(d0, d1, d2, r0, r1, r2);
+    else normalize3(d0, d1, d2, r0, r1, r2);     // skybox modelled at infinity
     // reflect(rayDir, (-1,0,0)) (render.frag:155); only .z is read
     const float k = 2.0f * ((-1.0f * r0 + 0.0f * r1) + 0.0f * r2);
     const float refl_z = r2 - k * 0.0f;
@@ -1225,13 +1267,31 @@ __device__ __forceinline__ void shade_sky(const KernelArgs &a, float d0, float d
     float sunFactor = gmax(0.0f, F.sun[0] * r0 + F.sun[1] * r1 + F.sun[2] * r2) - 1.0f;
     const float glow = vexp2(8.0f * sunFactor);
     sunFactor = vexp2(4000.0f * sunFactor) + 0.3f * glow;
-    const float rz = sqrtf(gmax(0.0f, refl_z));
-    float sky[3];
+    const float rz = sqrtf(gmax(0.0f, refl_z));   // (literal: r2 = d2 / |d| can lie below sqrt_ranged's 2^-96)
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         const float atm = gmix(F.scatterCol[i], F.spaceCol[i], rz);
-        sky[i] = gclamp(sunCol[i] * sunFactor + atm, 0.0f, 1.0f);
+        // clamp01 where r is finite: the sun term is then finite and >= +0 (a
+        // vexp2 result is), and atm, a lerp with rz in [0, 1] of two colours
+        // >= 0.2, is positive -- the sum is neither NaN nor -0.  A NaN
+        // direction (normalize(0), the mirror ray of a t = 0 hit) must stay
+        // NaN through the clamp: the select form.
+        const float v = sunCol[i] * sunFactor + atm;
+        sky[i] = RANGED ? clamp01(v) : gclamp(v, 0.0f, 1.0f);
     }
+}
+
+// ranged: wave-uniform (FrameConsts::rays_ranged for a view ray, false for any
+// other direction) -- one scalar branch, no per-wave test of the lengths
+// (a per-wave guard costs what it saves)
+__device__ __forceinline__ void shade_sky(const KernelArgs &a, float d0, float d1, float d2, float o[4],
+                          Counters &cnt, bool ranged = false) {
+    const FrameConsts &F = a.fc;
+    const float sunCol[3] = {1.4f, 1.0f, 0.5f};
+    float r0, r1, r2;
+    float sky[3];
+    if (ranged) sky_clear<true>(F, d0, d1, d2, r0, r1, r2, sky);
+    else sky_clear<false>(F, d0, d1, d2, r0, r1, r2, sky);
     r2 = fabsf(r2);                                                               // :179
     if (F.flags & VX_FLAG_NO_CLOUDS) {
         o[0] = sky[0]; o[1] = sky[1]; o[2] = sky[2]; o[3] = 1.0f;
@@ -1246,6 +1306,9 @@ __device__ __forceinline__ void shade_sky(const KernelArgs &a, float d0, float d
         sx = div_shared(r0, den, y); sy = div_shared(r1, den, y);
     }
     sx = sx * 0.1f; sy = sy * 0.1f;
+    // (literal roots: the ranged forms hold here too -- the outer argument is +0, >= 2^-75
+    // or NaN, the cloud factor in [2^-12, 1] or NaN -- but measured within noise on C3
+    // and, together with axis_normal, +1 % on C5: profiles/r07_ab.txt)
     const float sl = sqrtf(sqrtf(sx * sx + sy * sy));
     sx = sx * sl; sy = sy * sl;
     // render.frag:184-203 computes both the clouds and the mountains and keeps
@@ -1296,6 +1359,19 @@ __device__ __forceinline__ void white(const KernelArgs &a, float px, float py, f
 constexpr float kRoughScale = 0.00390625f;   // 1/256: 4 noise texels per voxel
 constexpr float kRoughAmp = 0.1f;
 
+// The axis normal of normal index ni (render.vert:14-17: 2 * axis, + 1 for the
+// negative direction): +-1 on its axis, +0 on the others.  The sign from the low
+// bit (bits(1.0f) | ni << 31) and one select per axis on ni >> 1, the compares
+// shared with the in-face axis selects, instead of two compare / select pairs
+// per axis: the same three values.
+__device__ __forceinline__ void axis_normal(int ni, float &n0, float &n1, float &n2) {
+    const float s = __uint_as_float(0x3f800000u | ((unsigned)ni << 31));
+    const int ax = ni >> 1;
+    n0 = ax == 0 ? s : 0.0f;
+    n1 = ax == 1 ? s : 0.0f;
+    n2 = ax == 2 ? s : 0.0f;
+}
+
 // ---------------- render.frag main(), block branch (render.frag:148-176, 207-251) ----------------
 // EXT: the extension instantiation (rough normals, soft shadows); has_ray:
 // rayDir is given (a surface seen in a reflection) instead of the camera ray
@@ -1308,9 +1384,8 @@ __device__ __forceinline__ float block_shade_factor(const KernelArgs &a, const S
     const FrameConsts &F = a.fc;
     const int ni = g.nidx;
     if (!(EXT && (F.flags & VX_FLAG_ROUGH))) return F.shadeFactor[ni];
-    const float n0 = ni == 0 ? 1.0f : (ni == 1 ? -1.0f : 0.0f);
-    const float n1 = ni == 2 ? 1.0f : (ni == 3 ? -1.0f : 0.0f);
-    const float n2 = ni == 4 ? 1.0f : (ni == 5 ? -1.0f : 0.0f);
+    float n0, n1, n2;
+    axis_normal(ni, n0, n1, n2);
     const int ax = ni >> 1;
     const float u = ax == 0 ? g.c1 + g.f1 : g.c0 + g.f0;
     const float v = ax == 2 ? g.c1 + g.f1 : g.c2 + g.f2;
@@ -1328,9 +1403,8 @@ __device__ __forceinline__ void shade_block(const KernelArgs &a, const Surf &g, 
                             float *ray_out = nullptr, int lit_given = -1) {
     const FrameConsts &F = a.fc;
     const int ni = g.nidx;
-    const float n0 = ni == 0 ? 1.0f : (ni == 1 ? -1.0f : 0.0f);
-    const float n1 = ni == 2 ? 1.0f : (ni == 3 ? -1.0f : 0.0f);
-    const float n2 = ni == 4 ? 1.0f : (ni == 5 ? -1.0f : 0.0f);
+    float n0, n1, n2;
+    axis_normal(ni, n0, n1, n2);
     float r0, r1, r2;
     if (EXT && has_ray) {
         r0 = q0; r1 = q1; r2 = q2;
@@ -1359,7 +1433,18 @@ __device__ __forceinline__ void shade_block(const KernelArgs &a, const Surf &g, 
     if (!(F.flags & VX_FLAG_NO_AO)) {                                                  // :223-225
         cnt.ao++;
         const float ambDist = sdf_lin(a, g.c0 + n0, g.c1 + n1, g.c2 + n2, g.f0, g.f1, g.f2);
-        const float ambFactor = gmin(1.0f - sqrtf(ambDist), 0.8f);
+        // sqrt_ranged: ambDist is 0 or >= 2^-73, inside its checked domain.  The
+        // sample is 255 times three nested lerps x * (1 - w) + y * w of texels
+        // that are 0 or >= RN(1/255) > 2^-8.  A weight w = u - floor(u) of
+        // u = p - 0.5 (p the rounded coordinate) is exact, and 0 or >= 2^-24:
+        // for p in [0.5, 1) u is a multiple of ulp(p) = 2^-24 and w = u; for
+        // p < 0.5, w = u + 1 >= 0.5; for |u| >= 0.5, w is a multiple of
+        // ulp(u) >= 2^-24.  w <= 1, so 1 - w is 0 or >= 2^-24 too.  All terms
+        // are >= +0, so a lerp is 0 or >= 2^-24 times its smallest non-zero
+        // input (RN is monotone, nothing is near underflow): >= 2^-32, 2^-56,
+        // 2^-80 after the three levels, times 255.  At most 255, so
+        // 1 - sqrt lies in [-15, 1], finite and never -0: fmin_fin.
+        const float ambFactor = fmin_fin(1.0f - sqrt_ranged(ambDist), 0.8f);
         amb0 = gmix(1.0f, F.shadeCol[0], ambFactor);
         amb1 = gmix(1.0f, F.shadeCol[1], ambFactor);
         amb2 = gmix(1.0f, F.shadeCol[2], ambFactor);
@@ -1585,7 +1670,11 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned v) {
 __device__ __forceinline__ uint32_t pack_rgba8(const float rgba[4]) {
     uint32_t pk = 0;
 #pragma unroll
-    for (int i = 0; i < 4; i++) pk |= (uint32_t)(gclamp(rgba[i], 0.0f, 1.0f) * 255.0f + 0.5f) << (8 * i);
+    // clamp01 for gclamp(x, 0, 1): the value only feeds * 255 + 0.5 and the
+    // truncating convert, so the two cases where the forms differ give one
+    // byte: -0 and +0 both 0.5 -> 0; a NaN stays NaN through the select form and
+    // converts to 0, and clamps to 0 (every float: profiles/r07_clamp_check.txt)
+    for (int i = 0; i < 4; i++) pk |= (uint32_t)(clamp01(rgba[i]) * 255.0f + 0.5f) << (8 * i);
     return pk;
 }
 
@@ -1595,6 +1684,13 @@ __device__ __forceinline__ void store_pixel(const KernelArgs &a, size_t idx, con
         reinterpret_cast<float4 *>(a.out)[idx] = make_float4(rgba[0], rgba[1], rgba[2], rgba[3]);
     else
         reinterpret_cast<uint32_t *>(a.out)[idx] = pack_rgba8(rgba);
+}
+// The RGBA8 pixel of an untiled frame at a 32-bit byte offset from a.out (the
+// saddr form, as ld_off: no 64-bit multiply-add and shifts per pixel): a frame
+// is at most 32768 x 32768 pixels (check_frame), so 4 * (py * w + px) <= 2^32 - 4.
+__device__ __forceinline__ void store_rgba8_frame(const KernelArgs &a, int px, int py, const float rgba[4]) {
+    const unsigned off = ((unsigned)py * (unsigned)a.w + (unsigned)px) << 2;
+    *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(a.out) + off) = pack_rgba8(rgba);
 }
 
 // output index of pixel (px, py), at (x, y) inside tile k of a tiled launch:
@@ -1930,7 +2026,7 @@ void k_render(KernelArgs a) {
                 n_block = n != 0 && g[0].id != 2;
             } else if (n == 0) {
                 n_sky = 1;
-                shade_sky(a, d0, d1, d2, rgba, cnt);
+                shade_sky(a, d0, d1, d2, rgba, cnt, F.rays_ranged != 0);
             } else {
                 // what a glass pane blends over is shaded FIRST: only its colour
                 // then stays live across the pane's shading (the record g[1]
@@ -2002,7 +2098,10 @@ if constexpr (!kGeneral) {
             rgba[3] = 1.0f;
             // each wave stores its own 8x8 tile (eight 32-B row pieces per RGBA8 wave
             // store): no block barrier, so a wave that finishes early frees its slot
-            store_pixel<FMT>(a, TILED ? (size_t)toidx : out_index<TILED>(a, tile_k, tx0 + lx, ty0 + ly, px, py), rgba);
+            if constexpr (!TILED && FMT == VX_PIXEL_RGBA8)
+                store_rgba8_frame(a, px, py, rgba);
+            else
+                store_pixel<FMT>(a, TILED ? (size_t)toidx : out_index<TILED>(a, tile_k, tx0 + lx, ty0 + ly, px, py), rgba);
             n_px = 1;
         }
     }

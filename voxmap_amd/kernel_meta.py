@@ -7,6 +7,8 @@ the render kernels must keep 8 waves/SIMD (<= 64 VGPRs) and must not carry a
 KernelArgs-sized private segment -- a pointer phi into the kernel arguments
 makes the compiler copy the whole 1.7 KB struct to scratch per thread, which
 fails silently (correct frames, ~14 GB of scratch traffic per frame).
+It also reads the kernel descriptors: every render kernel must run with
+DX10_CLAMP set (descriptor_modes).
 DESIGN.md §3 lists the measured budgets.
 """
 from __future__ import annotations
@@ -106,6 +108,28 @@ def kernels(lib: str) -> dict[str, dict[str, int]]:
     return out
 
 
+def descriptor_modes(lib: str) -> dict[str, dict[str, int]]:
+    """{mangled kernel name: {"dx10_clamp": 0/1, "ieee_mode": 0/1}} from the kernel
+    descriptors (the ``<kernel>.kd`` objects in .rodata, which llvm-objdump prints
+    as .amdhsa_* directives).  DX10_CLAMP is what makes the clamp output modifier
+    take a NaN to 0: vx_render.h's clamp01 relies on it."""
+    out: dict[str, dict[str, int]] = {}
+    with tempfile.TemporaryDirectory() as d:
+        for co in code_objects(lib, d):
+            txt = subprocess.run([_tool("llvm-objdump"), "-d", "-j", ".rodata", co], check=True,
+                                 capture_output=True, text=True).stdout
+            cur = None
+            for line in txt.splitlines():
+                m = re.match(r"\.amdhsa_kernel\s+(\S+)", line)
+                if m:
+                    cur = out.setdefault(m.group(1), {})
+                    continue
+                m = re.match(r"\s+\.amdhsa_(dx10_clamp|ieee_mode)\s+(\d+)", line)
+                if m and cur is not None:
+                    cur[m.group(1)] = int(m.group(2))
+    return out
+
+
 def render_params(name: str):
     """(FMT, STATS, TILED, EXT, F32IDX) of a mangled k_render instantiation, else None."""
     m = re.search(r"k_render(?:_gen)?ILi(\d)ELb(\d)ELb(\d)ELi(\d)ELb(\d)E", name)
@@ -192,6 +216,11 @@ def check(lib: str) -> dict[str, dict[str, int]]:
         general = p is not None and p[3] >= 5
         if not stats and v.get("vgpr_count", 0) > (80 if brick else GENERAL_VGPR_LIMIT if general else RENDER_VGPR_LIMIT):
             bad.append(f"{name}: {v['vgpr_count']} VGPRs > {RENDER_VGPR_LIMIT}")
+    # clamp01 (vx_render.h) relies on the clamp modifier taking a NaN to 0
+    modes = descriptor_modes(lib)
+    for name in render:
+        if modes.get(name, {}).get("dx10_clamp") != 1:
+            bad.append(f"{name}: DX10_CLAMP is not set in the kernel descriptor ({modes.get(name)})")
     for p, (loops, n) in hot_loop_spills(lib).items():
         if not loops:
             bad.append(f"k_render{p}: no march / primary loop found in the disassembly (check the parser)")
