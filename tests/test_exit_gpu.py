@@ -43,7 +43,7 @@ def _sun(el_deg, az_deg):
     return (math.cos(el) * math.cos(az), math.cos(el) * math.sin(az), math.sin(el))
 
 
-# (elevation, azimuth): windows (kx, ky) = (2, 1), (1, 2), (1, 1), (4, 4) in
+# (elevation, azimuth): windows (kx, ky) = (2, 1), (1, 2), (1, 1), (2, 3) in
 # different octants, a low sun (orthant copies) and a sun below the horizon
 SUNS = [(33, 30), (40, 120), (60, 210), (20, 300), (10, 45), (-20, 80)]
 
