@@ -36,7 +36,9 @@ extern "C" {
  * a zeroed dist_cap falls back to VX_FALLBACK_DIST_CAP where 64 does not fit,
  * and the sun march reads the doom table (VX_FLAG_NO_DOOM: without).
  * Still ABI 10, additive only: the ray queries (vx_query_rays, vx_pixel_ray,
- * vx_place_rays and their structs) change no existing signature or layout. */
+ * vx_place_rays and their structs) change no existing signature or layout.
+ * Still ABI 10, additive only: supersampled antialiasing (vx_render_aa,
+ * vx_aa_plan_for, vx_aa_plan) changes no existing signature or layout. */
 #define VX_ABI_VERSION 10
 
 /* error codes */
@@ -303,6 +305,56 @@ int vx_detile(vx_scene *scene, int w, int h, int tile_size, const int *tile_ids,
 int vx_render_bands(vx_scene *scene, const vx_frame_params *p, int w, int h, int band_rows,
                     const int *band_ids, int n_bands, int pixel_format, void *out_device,
                     int inplace, void *stream, vx_stats *stats);
+
+/* --- antialiasing (DESIGN.md §3 "Antialiasing") ------------------------------
+ * The reference draws into an antialiased canvas (map.js:7, getContext("webgl2",
+ * { alpha: false, antialias: true })).  Its MSAA sample count and positions are
+ * the browser's; a regular ss x ss supersample is defined by this header alone:
+ * the sub-pixel rays of a w*h frame at factor ss are the pixel rays of the
+ * (ss*w) x (ss*h) frame of the same vx_frame_params (the formula above).
+ *
+ * vx_render_aa: let H be the frame vx_render(scene, p, ss*w, ss*h, pixel_format)
+ * produces.  Output pixel (x, y) is the resolve of H's ss x ss block at
+ * (ss*x, ss*y), per channel:
+ *   VX_PIXEL_RGBA8:    (sum of the ss*ss bytes + ss*ss/2) / (ss*ss), integer
+ *                      arithmetic, rounding half up (a multisample resolve of
+ *                      the RGBA8 canvas: the panes have blended over canvas
+ *                      bytes per sample); A is 255.
+ *   VX_PIXEL_RGBA32F,  ss = 2: ((H(0,0) + H(1,0)) + (H(0,1) + H(1,1))) * 0.25f,
+ *                      indices (dx, dy), fp32 adds in this order, no contraction;
+ *                      ss = 4: that resolve applied twice (2x2 blocks, then 2x2
+ *                      of those results).
+ *   ss = 1:            exactly vx_render (same bytes, same stats, no resolve).
+ * ss is 1, 2 or 4.  Every flag, quality = 0 and soft shadows pass through: the
+ * samples are shaded by vx_render's kernels, each one in full (MSAA shades once
+ * per pixel and resolves coverage).
+ *
+ * H is never held whole: it is rendered in chunks of whole output rows (a
+ * multiple of 8 rows of H each, so no block straddles two chunks) into a
+ * stream-ordered intermediate of at most scratch_cap bytes on the caller's
+ * stream, each chunk resolved into its rows of out right after it.  scratch_cap
+ * 0: VX_AA_DEFAULT_SCRATCH; the least is one chunk of 8 rows of H,
+ * 8 * ss * w * bytes per pixel.  vx_aa_plan_for (a pure host function, no GPU)
+ * returns exactly the split vx_render_aa uses: chunk c covers output rows
+ * [c * chunk_rows_out, min(h, (c + 1) * chunk_rows_out)); scratch_bytes is the
+ * intermediate's size (0 for ss = 1).
+ *
+ * out: w*h pixels, row-major, top row first; a device out is aligned to 16
+ * bytes for RGBA32F and 4 for RGBA8, is stream-ordered and does not
+ * synchronise; a host out is staged and synchronises that stream only.  Calls
+ * on different streams of one scene are independent (no caller stream handle
+ * is kept).  stats: every counter is what vx_render reports for H (pixels =
+ * ss*ss*w*h, alg_bytes H's, summed over the chunks); kernel_ms is the chunk
+ * renders plus the resolve launches; vx_render's serialisation rule holds.
+ * VX_EINVAL before any GPU call: ss not 1, 2 or 4; ss*w or ss*h above 32768;
+ * scratch_cap below one chunk; a NULL scene, params or out. */
+#define VX_AA_MAX 4
+#define VX_AA_DEFAULT_SCRATCH ((size_t)128 << 20)   /* measured: DESIGN.md §3 "Antialiasing" */
+int vx_render_aa(vx_scene *scene, const vx_frame_params *p, int w, int h, int ss,
+                 int pixel_format, void *out, int out_on_device, void *stream,
+                 size_t scratch_cap, vx_stats *stats);
+typedef struct vx_aa_plan { int ss, chunk_rows_out, n_chunks; size_t scratch_bytes; } vx_aa_plan;
+int vx_aa_plan_for(int w, int h, int ss, int pixel_format, size_t scratch_cap, vx_aa_plan *out);
 
 /* --- ray queries: picking and place-label visibility (DESIGN.md "Ray queries") ---
  * The reference's page labels every place without asking whether a building

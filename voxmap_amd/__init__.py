@@ -13,6 +13,8 @@ from .renderer import (Frame, MultiGPU, Scene, blob_encrypt, decode, field_build
                        params_to_dict, sun_from_hour, sun_samples, vertex2d,
                        HIT_DTYPE, PLACE_VIEW_DTYPE, RAY_DTYPE, SURFACE_DTYPE, hits_visible, pixel_ray, place_rays)
 from ._abi import QueryStats, RAY_INVALID
+from ._abi import AA_DEFAULT_SCRATCH, AA_MAX
+from .renderer import aa_plan
 
 __all__ = [
     "Scene", "Frame", "FrameParams", "Stats", "VoxmapError", "lib", "make_frame", "frame_from_orbit",
@@ -23,5 +25,5 @@ __all__ = [
     "FLAG_UNIT_GBUF", "FLAG_GLASS_ORDER", "FLAG_GLASS_SINGLE", "FLAG_REFLECT_ALL", "sun_samples", "field_build_gpu", "FORMAT_GRID",
     "MultiGPU", "mgpu_unique_id", "mgpu_band_rows", "mgpu_bands", "mgpu_transfers", "vertex2d",
     "RAY_DTYPE", "HIT_DTYPE", "SURFACE_DTYPE", "PLACE_VIEW_DTYPE", "QueryStats", "RAY_INVALID", "pixel_ray",
-    "place_rays", "hits_visible",
+    "place_rays", "hits_visible", "aa_plan", "AA_MAX", "AA_DEFAULT_SCRATCH",
 ]

@@ -98,6 +98,15 @@ class ExitInfo(C.Structure):
     _fields_ = [("kind", C.c_int), ("octant", C.c_int), ("kx", C.c_int), ("ky", C.c_int), ("build_ms", C.c_float)]
 
 
+AA_MAX = 4
+AA_DEFAULT_SCRATCH = 128 << 20                  # vx_render_aa's scratch_cap = 0
+
+
+class AaPlan(C.Structure):
+    """vx_aa_plan: how vx_render_aa splits the frame into chunks of output rows."""
+    _fields_ = [("ss", C.c_int), ("chunk_rows_out", C.c_int), ("n_chunks", C.c_int), ("scratch_bytes", C.c_size_t)]
+
+
 RAY_INVALID = -1
 MAX_QUERY_RAYS = 1 << 26
 
@@ -183,6 +192,9 @@ SIGNATURES = [
     ("vx_pixel_ray", C.c_int, [C.POINTER(FrameParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Ray)]),
     ("vx_place_rays", C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_void_p, C.c_int, C.c_void_p,
                                 C.c_void_p]),
+    ("vx_render_aa", C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                               C.c_int, C.c_void_p, C.c_size_t, C.POINTER(Stats)]),
+    ("vx_aa_plan_for", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(AaPlan)]),
     ("vx_last_error", C.c_char_p, []),
     ("vx_abi_version", C.c_int, []),
 ]

@@ -17,7 +17,7 @@ OUT = os.path.join(HERE, "libvoxmap_hip.so")
 # the render kernel's EXT modes compile in units of their own (vx_render.h), listed
 # first: they are the long ones, and the pool starts them first
 SOURCES = ["vx_render_e56.hip", "vx_render_e2.hip", "vx_render_e1.hip", "vx_render_e0.hip", "vx_render_e3.hip",
-           "vx_render_e4.hip", "vx_kernels.hip", "vx_field_gpu.hip", "vx_query.hip", "vx_api.cpp", "vx_host.cpp",
+           "vx_render_e4.hip", "vx_kernels.hip", "vx_field_gpu.hip", "vx_query.hip", "vx_resolve.hip", "vx_api.cpp", "vx_host.cpp",
            "vx_codec.cpp", "vx_field.cpp", "vx_frame.cpp", "vx_mgpu.cpp"]
 HEADERS = ["vx_internal.h", "vx_render.h", "vx_device.h"]
 ARCH = os.environ.get("VOXMAP_ARCH", "gfx950")

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -643,7 +644,87 @@ static int do_query(vx_scene *s, const void *d_rays, int n, void *d_hits, hipStr
     return VX_OK;
 }
 
+// Chunks [c0, c1) of vx_render_aa's plan into their rows of the w x h device frame d_out:
+// chunk c is band c of the (ss*w) x (ss*h) frame at band height ss * chunk_rows_out,
+// rendered compact into `scratch` by the band path and resolved right behind it on st,
+// while its bytes are still on-die.  One id list 0 .. n_chunks - 1 serves every chunk
+// (chunk c reads the one id at offset c) and stays pinned until the last is enqueued: a
+// call adds one list to the cache whatever its height.  Every chunk finds the sun copy
+// the first one built (frame_exit).  stats: the chunks' counters summed, their kernel
+// times plus the resolves'.
+static int aa_chunks(vx_scene *s, const vx_frame_params *p, int w, int h, int fmt, const vx_aa_plan &plan, int c0, int c1,
+                     void *scratch, void *d_out, hipStream_t st, vx_stats *stats) {
+    const int ss = plan.ss, W = ss * w, H = ss * h;
+    std::vector<int> ids((size_t)plan.n_chunks);
+    for (int c = 0; c < plan.n_chunks; c++) ids[(size_t)c] = c;
+    ListRef lr;
+    VX_CHECK(list_acquire(s, st, ids.data(), plan.n_chunks, lr));
+    TileSpec t;
+    t.tw = (W + VX_TILE_ALIGN_X - 1) / VX_TILE_ALIGN_X * VX_TILE_ALIGN_X;
+    t.th = ss * plan.chunk_rows_out;
+    t.pitch = W;
+    t.tiles_x = 1;
+    t.n = 1;
+    vx_stats sum;
+    std::memset(&sum, 0, sizeof sum);
+    for (int c = c0; c < c1; c++) {
+        const int y0 = c * plan.chunk_rows_out, rows = std::min(plan.chunk_rows_out, h - y0);
+        t.ids = lr.b->d.get() + c;
+        vx_stats cs;
+        VX_CHECK(do_render(s, p, W, H, t, fmt, scratch, st, stats ? &cs : nullptr));
+        if (stats) VX_HIP(hipEventRecord(s->ev0.get(), st));
+        const int rc = launch_resolve(scratch, static_cast<char *>(d_out) + (size_t)y0 * w * pixel_bytes(fmt), w, rows, ss,
+                                      W, fmt, st);
+        if (rc) return set_error(VX_EDEVICE, std::string("resolve launch failed: ") + hipGetErrorString((hipError_t)rc));
+        if (stats) {
+            float ms = 0.0f;
+            VX_HIP(hipEventRecord(s->ev1.get(), st));
+            VX_HIP(hipEventSynchronize(s->ev1.get()));
+            VX_HIP(hipEventElapsedTime(&ms, s->ev0.get(), s->ev1.get()));
+            uint64_t *a = &sum.pixels;
+            const uint64_t *b = &cs.pixels;
+            for (size_t i = 0; i < offsetof(vx_stats, kernel_ms) / sizeof(uint64_t); i++) a[i] += b[i];
+            sum.kernel_ms += cs.kernel_ms + (double)ms;
+        }
+    }
+    if (stats) *stats = sum;
+    return VX_OK;
+}
+
 extern "C" {
+
+int vx_render_aa(vx_scene *s, const vx_frame_params *p, int w, int h, int ss, int fmt, void *out, int out_on_device,
+                 void *stream, size_t scratch_cap, vx_stats *stats) {
+    // the argument checks need no scene and come first; none of them touches the GPU
+    if (!p || !out) return set_error(VX_EINVAL, "vx_render_aa: null params or out");
+    vx_aa_plan plan;
+    VX_CHECK(vx_aa_plan_for(w, h, ss, fmt, scratch_cap, &plan));
+    if (!s) return set_error(VX_EINVAL, "vx_render_aa: null scene");
+    if (ss == 1) return vx_render(s, p, w, h, fmt, out, out_on_device, stream, stats);
+    VX_CHECK(check_render(s, p, ss * w, ss * h, fmt));
+    if (out_on_device && ((uintptr_t)out & (fmt == VX_PIXEL_RGBA32F ? 15u : 3u)))
+        return set_error(VX_EINVAL, "vx_render_aa: a device out must be aligned to 16 bytes (RGBA32F) or 4 (RGBA8)");
+    VX_HIP(hipSetDevice(s->device));
+    hipStream_t st = stream_of(s, stream);
+    const size_t bytes = (size_t)w * h * pixel_bytes(fmt);
+    void *scratch = nullptr, *d_out = out_on_device ? out : nullptr;
+    int rc = VX_OK;
+    hipError_t e = hipMallocAsync(&scratch, plan.scratch_bytes, st);
+    if (e == hipSuccess && !out_on_device) e = hipMallocAsync(&d_out, bytes, st);
+    if (e != hipSuccess) rc = set_error(VX_EDEVICE, std::string("vx_render_aa: staging failed: ") + hipGetErrorString(e));
+    if (rc == VX_OK) rc = aa_chunks(s, p, w, h, fmt, plan, 0, plan.n_chunks, scratch, d_out, st, stats);
+    if (rc == VX_OK && !out_on_device) {
+        e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = set_error(VX_EDEVICE, std::string("vx_render_aa: readback failed: ") + hipGetErrorString(e));
+    }
+    if (scratch) (void)hipFreeAsync(scratch, st);
+    if (!out_on_device) {
+        if (d_out) (void)hipFreeAsync(d_out, st);
+        (void)hipStreamSynchronize(st);
+    }
+    return rc;
+}
 
 void vx_scene_destroy(vx_scene *s) {
     if (!s) return;

@@ -12,7 +12,9 @@
 // usage: vxrender --map FILE [--format bin|gz|blob|grid] [--key JWK_K] [--noise FILE]
 //                 [--dims X,Y,Z] [--size W,H] [--camera K0|K1|K2 | --orbit sx,sy,sz,rx,ry,rz]
 //                 [--hour H] [--time T] [--flags N] [--full] [--samples N] [--radius R]
-//                 [--frames N] [--device D] [--ranks N] [--out FILE.ppm|FILE.rgba]
+//                 [--frames N] [--device D] [--ranks N] [--aa N] [--out FILE.ppm|FILE.rgba]
+// --aa N (1, 2 or 4): N x N samples per pixel resolved on the device (vx_render_aa), as the
+// page's canvas is antialiased (map.js:7); not with --ranks.
 // The key may also come from the VOXMAP_KEY environment variable (never a file in the repository).
 #include <hip/hip_runtime.h>
 
@@ -68,7 +70,7 @@ std::vector<unsigned char> read_all(const std::string &path) {
 
 int main(int argc, char **argv) {
     std::string map, noise, key, out, format = "auto";
-    int dims[3] = {1024, 256, 32}, w = 3840, h = 2160, frames = 1, device = 0, samples = 0, ranks = 0;
+    int dims[3] = {1024, 256, 32}, w = 3840, h = 2160, frames = 1, device = 0, samples = 0, ranks = 0, aa = 0;
     double sbj[3] = {381.5, 128.1, 40.0}, rot[3] = {1.1, 0.0, 0.6};   // camera K1 (voxmap_amd/presets.py)
     double hour = 1.0, time = 123.0, radius = 0.03;
     unsigned flags = 0;
@@ -101,18 +103,20 @@ int main(int argc, char **argv) {
         else if (a == "--frames") frames = std::atoi(next());
         else if (a == "--device") device = std::atoi(next());
         else if (a == "--ranks") ranks = std::atoi(next());
+        else if (a == "--aa") aa = std::atoi(next());
         else if (a == "--out") out = next();
         else if (a == "--help" || a == "-h") {
             std::printf("usage: vxrender --map FILE [--format bin|gz|blob|grid] [--key K] [--noise FILE] "
                         "[--dims X,Y,Z] [--size W,H] [--camera K0|K1|K2 | --orbit sx,sy,sz,rx,ry,rz] [--hour H] "
                         "[--time T] [--flags N] [--full] [--samples N] [--radius R] [--frames N] [--device D] "
-                        "[--ranks N] [--out FILE.ppm|FILE.rgba]\n(ABI version %d)\n", vx_abi_version());
+                        "[--ranks N] [--aa N] [--out FILE.ppm|FILE.rgba]\n(ABI version %d)\n", vx_abi_version());
             return 0;
         } else die("unknown option " + a);
     }
     if (map.empty()) die("--map is required (see --help)");
     if (key.empty() && std::getenv("VOXMAP_KEY")) key = std::getenv("VOXMAP_KEY");
     if (ranks < 0 || ranks > 64) die("--ranks must be in 0..64");
+    if (aa != 0 && ranks >= 1) die("--aa is not available with --ranks");
 
     // --ranks N: fork the rank processes now, before anything touches the GPU
     int rank = 0, nranks = 1, uid_pipe[2] = {-1, -1};
@@ -196,6 +200,7 @@ int main(int argc, char **argv) {
     const int band_rows = vx_mgpu_band_rows(h, nranks > 0 ? nranks : 1, 64);   // the balanced deal
     auto draw = [&](vx_stats *s) {
         if (mg) check(vx_mgpu_render(mg, &p, w, h, band_rows, VX_PIXEL_RGBA8, d_out, stream, s), "vx_mgpu_render");
+        else if (aa) check(vx_render_aa(scene, &p, w, h, aa, VX_PIXEL_RGBA8, d_out, 1, stream, 0, s), "vx_render_aa");
         else check(vx_render(scene, &p, w, h, VX_PIXEL_RGBA8, d_out, 1, stream, s), "vx_render");
     };
     vx_stats st = {};
@@ -211,13 +216,14 @@ int main(int argc, char **argv) {
     (void)hipEventElapsedTime(&ms, e0, e1);
     ms /= (float)frames;
     const double rays = (double)(st.pixels + st.shadow_rays + st.reflect_rays);
+    const std::string aa_field = aa ? ", \"aa\": " + std::to_string(aa) : "";   // only with --aa
     if (rank == 0)
         std::printf("{\"size\": [%d, %d], \"field\": [%d, %d, %d], \"flags\": %u, \"shadow_samples\": %d, "
                     "\"ranks\": %d, \"scene_build_s\": %.3f, \"ms_per_frame\": %.4f, \"fps\": %.1f, "
                     "\"rank0_pixels\": %llu, \"rank0_mrays_per_s\": %.1f, \"rank0_alg_gbps\": %.1f, "
-                    "\"rank0_rays_per_frame\": %.0f}\n",
+                    "\"rank0_rays_per_frame\": %.0f%s}\n",
                     w, h, dims[0], dims[1], dims[2], flags, samples, nranks, scene_s, ms, 1000.0 / ms,
-                    (unsigned long long)st.pixels, rays / ms / 1e3, (double)st.alg_bytes / ms / 1e6, rays);
+                    (unsigned long long)st.pixels, rays / ms / 1e3, (double)st.alg_bytes / ms / 1e6, rays, aa_field.c_str());
     std::fflush(stdout);
     if (mg) vx_mgpu_destroy(mg);
 

@@ -382,6 +382,34 @@ int vx_field_build(const uint8_t *color, int X, int Y, int Z, uint8_t *rgba_out,
 
 int vx_noise_synth(uint32_t seed, int w, int h, uint8_t *rgba_out) { return noise_synth(seed, w, h, rgba_out); }
 
+// The split of vx_render_aa: chunks of whole output rows whose ss * rows is a
+// multiple of 8 (the render block's height, and of every ss), as many as
+// scratch_cap holds of the (ss*w)-pixel rows of the hi-res frame.
+int vx_aa_plan_for(int w, int h, int ss, int pixel_format, size_t scratch_cap, vx_aa_plan *out) {
+    if (!out) return set_error(VX_EINVAL, "vx_aa_plan_for: null plan");
+    if (ss != 1 && ss != 2 && ss != VX_AA_MAX) return set_error(VX_EINVAL, "ss (supersample) must be 1, 2 or 4");
+    if (pixel_format != VX_PIXEL_RGBA8 && pixel_format != VX_PIXEL_RGBA32F)
+        return set_error(VX_EINVAL, "unknown pixel format");
+    if (w <= 0 || h <= 0 || w > 32768 / ss || h > 32768 / ss)
+        return set_error(VX_EINVAL, "frame size out of range: ss * w and ss * h must be in 1 .. 32768");
+    if (ss == 1) {
+        *out = vx_aa_plan{1, h, 1, 0};
+        return VX_OK;
+    }
+    const size_t row_bytes = (size_t)ss * (size_t)w * (pixel_format == VX_PIXEL_RGBA32F ? 16u : 4u);
+    static_assert(VX_AA_DEFAULT_SCRATCH >= (size_t)VX_TILE_ALIGN_Y * 32768 * 16, "the default holds any minimal chunk");
+    const size_t cap = scratch_cap ? scratch_cap : VX_AA_DEFAULT_SCRATCH;
+    if (cap < VX_TILE_ALIGN_Y * row_bytes)
+        return set_error(VX_EINVAL, "scratch_cap is below one chunk (8 * ss * w * bytes per pixel)");
+    const size_t frame_rows = ((size_t)ss * (size_t)h + VX_TILE_ALIGN_Y - 1) / VX_TILE_ALIGN_Y * VX_TILE_ALIGN_Y;
+    const size_t rows = std::min(cap / row_bytes / VX_TILE_ALIGN_Y * VX_TILE_ALIGN_Y, frame_rows);   // of the hi-res frame
+    out->ss = ss;
+    out->chunk_rows_out = (int)(rows / (size_t)ss);
+    out->n_chunks = (h + out->chunk_rows_out - 1) / out->chunk_rows_out;
+    out->scratch_bytes = rows * row_bytes;
+    return VX_OK;
+}
+
 int vx_mgpu_bands(int h, int band_rows, int nranks, int rank, int *ids, int cap) {
     if (h <= 0 || band_rows <= 0 || nranks <= 0 || rank < 0 || rank >= nranks)
         return set_error(VX_EINVAL, "vx_mgpu_bands: bad arguments");

@@ -245,6 +245,10 @@ int launch_query(const QueryArgs &a, void *stream);
 int launch_render(const KernelArgs &a, int pixel_format, void *stream);
 int launch_detile(const void *tiles, void *frame, int w, int h, int tile_size, int tiles_x,
                   const int *tile_ids, int n_tiles, int pixel_format, void *stream);
+// The resolve of vx_render_aa (vx_resolve.hip): `rows` output rows of w pixels into dst from
+// ss * rows rows of ss * w pixels at src, rows src_pitch pixels apart (voxmap.h: the definition).
+// src 16-byte aligned, dst aligned to its pixel; ss 2 or 4.
+int launch_resolve(const void *src, void *dst, int w, int rows, int ss, int src_pitch, int pixel_format, void *stream);
 // map.bin texels (A = 0) from a device palette grid (vx_field_gpu.hip)
 int field_build_device(const uint8_t *d_col, uint32_t *d_rgba, int X, int Y, int Z, void *stream);
 // A channel of octant copy `oct` (in place in a linear grid upload)

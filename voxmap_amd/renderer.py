@@ -243,6 +243,28 @@ class Scene:
                               C.byref(st) if st is not None else None))
         return st
 
+    def render_aa(self, frame: Frame, supersample: int, *, pixel_format=_abi.PIXEL_RGBA32F, stats: bool = False,
+                  scratch_cap: int = 0):
+        """``frame`` with supersample x supersample samples per pixel on a regular grid, resolved
+        on the device (vx_render_aa); returns (image[h, w, 4], Stats or None).  The counters are
+        those of the (supersample * w) x (supersample * h) frame."""
+        w, h = frame.width, frame.height
+        out = np.empty((h, w, 4), np.float32 if pixel_format == _abi.PIXEL_RGBA32F else np.uint8)
+        st = Stats() if stats else None
+        check(lib().vx_render_aa(self.handle, C.byref(frame.params), w, h, int(supersample), pixel_format,
+                                 out.ctypes.data, 0, None, int(scratch_cap), C.byref(st) if st is not None else None))
+        return out, st
+
+    def render_aa_device(self, frame: Frame, supersample: int, out_ptr: int, *, pixel_format=_abi.PIXEL_RGBA32F,
+                         stats: bool = False, scratch_cap: int = 0, stream=None):
+        """render_aa into a device buffer of w * h pixels (e.g. a torch tensor's data_ptr());
+        stream-ordered, no synchronisation unless ``stats``."""
+        st = Stats() if stats else None
+        check(lib().vx_render_aa(self.handle, C.byref(frame.params), frame.width, frame.height, int(supersample),
+                                 pixel_format, C.c_void_p(out_ptr), 1, C.c_void_p(stream) if stream else None,
+                                 int(scratch_cap), C.byref(st) if st is not None else None))
+        return st
+
     def render_tiles(self, frame: Frame, tile_size: int, tile_ids, out_ptr: int, *,
                      pixel_format=_abi.PIXEL_RGBA8, stream=None, stats: bool = False):
         ids = np.ascontiguousarray(np.asarray(tile_ids, dtype=np.int32))
@@ -313,16 +335,30 @@ class Scene:
         return views, hits_visible(self.query_rays(rays))
 
     def draw_scene(self, projection_matrix, position, sun, frame, time, *, width, height, mode_3d=True,
-                   pixel_format=_abi.PIXEL_RGBA8):
-        """drawScene(projection_matrix, position, sun, frame, time) of render.js:267, returning the canvas."""
+                   pixel_format=_abi.PIXEL_RGBA8, supersample=1):
+        """drawScene(projection_matrix, position, sun, frame, time) of render.js:267, returning the canvas;
+        supersample > 1: antialiased (render_aa), as the page's canvas is (map.js:7)."""
         p = frame_from_matrix(projection_matrix, position)
         for i in range(3):
             p.sun_dir[i] = float(sun[i])
         p.quality = 1 if mode_3d else 0
         p.frame = int(frame)
         p.time = float(time) % 1000.0
-        img, _ = self.render(Frame(p, int(width), int(height)), pixel_format=pixel_format)
+        fr = Frame(p, int(width), int(height))
+        if int(supersample) > 1:
+            img, _ = self.render_aa(fr, int(supersample), pixel_format=pixel_format)
+        else:
+            img, _ = self.render(fr, pixel_format=pixel_format)
         return img
+
+
+def aa_plan(w: int, h: int, supersample: int, pixel_format: int, scratch_cap: int = 0) -> dict:
+    """How vx_render_aa splits a w x h frame (vx_aa_plan_for, a pure host function): {"ss",
+    "chunk_rows_out", "n_chunks", "scratch_bytes"}; chunk c covers output rows
+    [c * chunk_rows_out, min(h, (c + 1) * chunk_rows_out))."""
+    plan = _abi.AaPlan()
+    check(lib().vx_aa_plan_for(int(w), int(h), int(supersample), int(pixel_format), int(scratch_cap), C.byref(plan)))
+    return {k: int(getattr(plan, k)) for k, _ in plan._fields_}
 
 
 def mgpu_unique_id() -> bytes:
