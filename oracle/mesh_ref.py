@@ -4,7 +4,7 @@ SURVEY §8 f-4.  The reference never ray-marches primary rays: it rasterises
 the greedy quad mesh of src/gen/sdf.cpp:281-356 (vertex.bin) with depth test,
 back-face culling and glass drawn last with alpha blending (render.js:82-91).
 The build replaces that raster by a traversal of the field
-(oracle/vxo_render.c walk(), vx_kernels.hip primary()).  This module restates
+(oracle/vxo_render.c walk(), vx_walk.h primary()).  This module restates
 the mesher and intersects the camera rays with its quads, giving an
 independent answer to "which face does this pixel show" to check the
 traversal against.

@@ -1,5 +1,5 @@
 """Every render instantiation runs with DX10_CLAMP set (CPU only: reads the kernel
-descriptors of the in-tree library).  vx_render.h's clamp01 is the hardware
+descriptors of the in-tree library).  vx_math.h's clamp01 is the hardware
 clamp, which takes a NaN to 0 only under DX10_CLAMP; kernel_meta.check, which
 build() runs, refuses a library without it, and the resource limits of
 tests/test_kernel_resources.py are part of the same check."""

@@ -1,6 +1,6 @@
 """The RGBA8 frame is the RGBA32F frame packed: byte = floor(clamp(v, 0, 1) * 255 + 0.5).
 
-pack_rgba8 clamps with the hardware's clamp (vx_render.h clamp01) where the
+pack_rgba8 clamps with the hardware's clamp (vx_math.h clamp01) where the
 contract spells min(max(v, 0), 1) as two selects; the forms differ on NaN and
 -0 only, and both then give byte 0.  Here every pose of tests/test_poses.py --
 the degenerate ones included: t0_hit with mirrors on every surface has NaN in

@@ -39,7 +39,9 @@ def listing(lib: str) -> dict[str, list[str]]:
                     continue
                 ins = line.split("//")[0].strip()
                 ins = re.sub(r"<[^>]*>", "<L>", ins)              # branch targets
-                if ins:
+                # "...": objdump's mark for the zero padding up to the next kernel's alignment, absent
+                # after the last kernel of a unit -- where a kernel stands in its unit, not its code
+                if ins and ins != "...":
                     cur.append(ins)
     return out
 

@@ -1,4 +1,4 @@
-// Exhaustive check on gfx950 of vx_render.h's proven forms against the GLSL
+// Exhaustive check on gfx950 of vx_math.h's proven forms against the GLSL
 // select forms they replace, over all 2^32 float bit patterns x:
 //   pack   the RGBA8 byte (uint)(c(x) * 255 + 0.5) with c = gclamp(x, 0, 1)
 //          (two v_cmp + v_cndmask pairs) against c = clamp01 (v_med3 / the clamp
@@ -32,7 +32,7 @@ __device__ __forceinline__ float clamp_mod(float x) {
 }
 __device__ __forceinline__ unsigned byte_of(float c) { return (unsigned)(c * 255.0f + 0.5f); }
 
-__device__ __forceinline__ float sqrt_ranged(float x) {   // vx_render.h
+__device__ __forceinline__ float sqrt_ranged(float x) {   // vx_math.h
     const float s = __builtin_amdgcn_sqrtf(x);
     const float dn = __uint_as_float(__float_as_uint(s) - 1u), up = __uint_as_float(__float_as_uint(s) + 1u);
     float r = __builtin_fmaf(-dn, s, x) <= 0.0f ? dn : s;

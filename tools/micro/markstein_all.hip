@@ -3,7 +3,7 @@
 // against the IEEE quotient a / b for EVERY pair of significands
 // a, b in [1, 2) (2^46 pairs).  Scaling a or b by a power of two scales every
 // intermediate exactly while nothing under/overflows, and the sign is
-// symmetric, so 0 mismatches here means div_const (vx_kernels.hip) is the
+// symmetric, so 0 mismatches here means div_const (vx_math.h) is the
 // IEEE quotient for all normal a, b whose quotient and residual stay normal —
 // which licenses a per-pixel divisor (normalize3), not only per-frame ones.
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// Exhaustive check on gfx950 of vx_kernels.hip's sqrt_ranged: hipcc's
+// Exhaustive check on gfx950 of vx_math.h's sqrt_ranged: hipcc's
 // correctly rounded sqrtf (-fhip-fp32-correctly-rounded-divide-sqrt) is
 // v_sqrt_f32 plus a one-ulp residual correction, wrapped in a 2^32 scaling for
 // inputs below 2^-96 and a class test for zero / inf.  sqrt_ranged keeps the

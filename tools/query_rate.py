@@ -25,8 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def palette_rgba8() -> np.ndarray:
-    """kPalette of csrc/vx_render.h as the RGBA8 words a PRIMARY_ONLY frame holds (pack_rgba8)."""
-    src = open(os.path.join(ROOT, "voxmap_amd", "csrc", "vx_render.h")).read()
+    """kPalette of csrc/vx_loads.h as the RGBA8 words a PRIMARY_ONLY frame holds (pack_rgba8)."""
+    src = open(os.path.join(ROOT, "voxmap_amd", "csrc", "vx_loads.h")).read()
     body = re.search(r"kPalette\[22\]\[3\] = \{(.*?)\n\};", src, re.S).group(1)
     pal = np.array([[float(v.rstrip("f")) for v in row.split(",")] for row in re.findall(r"\{([^{}]+)\}", body)],
                    np.float32)

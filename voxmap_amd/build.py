@@ -17,9 +17,12 @@ OUT = os.path.join(HERE, "libvoxmap_hip.so")
 # the render kernel's EXT modes compile in units of their own (vx_render.h), listed
 # first: they are the long ones, and the pool starts them first
 SOURCES = ["vx_render_e56.hip", "vx_render_e2.hip", "vx_render_e1.hip", "vx_render_e0.hip", "vx_render_e3.hip",
-           "vx_render_e4.hip", "vx_kernels.hip", "vx_field_gpu.hip", "vx_query.hip", "vx_resolve.hip", "vx_api.cpp", "vx_host.cpp",
-           "vx_codec.cpp", "vx_field.cpp", "vx_frame.cpp", "vx_mgpu.cpp"]
-HEADERS = ["vx_internal.h", "vx_render.h", "vx_device.h"]
+           "vx_render_e4.hip", "vx_dispatch.hip", "vx_scene_prep.hip", "vx_field_gpu.hip", "vx_query.hip",
+           "vx_resolve.hip", "vx_api.cpp", "vx_host.cpp", "vx_codec.cpp", "vx_field.cpp", "vx_frame.cpp", "vx_mgpu.cpp"]
+# every header under csrc/: an object is rebuilt when any of them is newer (the
+# render kernel's stage headers, vx_math.h .. vx_pixel.h, are included by vx_render.h)
+HEADERS = ["vx_internal.h", "vx_device.h", "vx_math.h", "vx_loads.h", "vx_march.h", "vx_walk.h", "vx_sample.h",
+           "vx_shade.h", "vx_pixel.h", "vx_render.h"]
 ARCH = os.environ.get("VOXMAP_ARCH", "gfx950")
 # -fno-slp-vectorize: packed FP32 (v_pk_*) issues at the cost of two scalar ops
 # on gfx950 (profiles/r01_valu_costs.txt), so SLP packing only adds moves.

@@ -22,7 +22,7 @@
 
 using namespace vx;
 
-#ifndef VX_QSPEC   // as vx_render.h: the fp32-index walk loads its quad offsets beside every prim word (d_qcopy)
+#ifndef VX_QSPEC   // as vx_walk.h: the fp32-index walk loads its quad offsets beside every prim word (d_qcopy)
 #define VX_QSPEC 1
 #endif
 
@@ -226,13 +226,13 @@ static hipError_t step_arrays(vx_scene *s, const SceneInputs &in, Scratch &sc) {
 }
 
 // march copy of the sun channels: int8 inside a border of -1 ("left the grid"), so the
-// march's loaded value carries the exit test (vx_kernels.hip march_fast); values <= Z <= 126
+// march's loaded value carries the exit test (vx_march.h march_pad_from); values <= Z <= 126
 static hipError_t march_copies(vx_scene *s, const SceneInputs &in, Scratch &sc) {
     const int X = s->X, Y = s->Y, Z = s->Z;
     hipStream_t st = s->stream.get();
     const size_t sxy = (size_t)(X + 2 * (Z + 2)) * (Y + 2 * (Z + 2));
     // the march's byte offset is 0x4B000000 + x + Xp*y + XpYp*z from fp32 bit patterns
-    // (vx_kernels.hip march_pad): the padded plane below 2^23, the sum below 2^32
+    // (vx_march.h march_pad): the padded plane below 2^23, the sum below 2^32
     if (!(Z <= 126 && in.max_rg <= Z && sxy < (1u << 23) && sxy * (Z + 2 * (Z + 2) + 3) + 0x4B000000ull < (1ull << 32)))
         return hipSuccess;
     s->SB = Z + 2;

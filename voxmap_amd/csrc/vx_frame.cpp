@@ -163,7 +163,7 @@ void frame_consts(const vx_frame_params &p, int w, int h, int X, int Y, int Z, i
     float dirs[VX_MAX_SHADOW_SAMPLES][3];
     sun_samples(p.sun_dir, p.sun_radius, fc.n_sun, dirs);
     for (int k = 0; k < fc.n_sun; k++) sun_ray(dirs[k], fc.sun_k[k]);
-    // the pooled soft-shadow march (vx_kernels.hip) runs one loop specialised on
+    // the pooled soft-shadow march (vx_render.h k_render) runs one loop specialised on
     // the axis signs for every sample: only when they all agree
     fc.soft_sg = -1;
     fc.soft_lg = 0;

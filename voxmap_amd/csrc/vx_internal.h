@@ -134,7 +134,7 @@ enum StatSlot {
     ST_MARCH_SLOTS, ST_SHADOW_RESOLVED, ST_COUNT
 };
 
-// Field data in HBM (vx_kernels.hip): `prim` = 8 copies (one
+// Field data in HBM (vx_loads.h): `prim` = 8 copies (one
 // per ray octant) of the X x Y x Z grid, u32 colour | air-box extents << 8,
 // 16, 24, inside a border of pad = cap sentinel cells; `sun` = R and G
 // channels (u8); `rg` = R | G << 8 (u16).
@@ -241,8 +241,16 @@ struct QueryArgs {
 enum QueryStatSlot { QS_INVALID = 0, QS_HITS, QS_GLASS, QS_FETCH, QS_CAP_HITS, QS_COUNT };
 int launch_query(const QueryArgs &a, void *stream);
 
-// Launchers (vx_kernels.hip).  Return a hipError_t as int.
+// Launchers (vx_dispatch.hip).  Return a hipError_t as int.
 int launch_render(const KernelArgs &a, int pixel_format, void *stream);
+// the per-mode launchers launch_render picks from (vx_render_e*.hip: each is
+// launch_render_ext of vx_render.h over that unit's k_render instantiations)
+int launch_render_e0(const KernelArgs &a, int fmt, unsigned gx, unsigned gy, void *stream);
+int launch_render_e1(const KernelArgs &a, int fmt, unsigned gx, unsigned gy, void *stream);
+int launch_render_e2(const KernelArgs &a, int fmt, unsigned gx, unsigned gy, void *stream);
+int launch_render_e3(const KernelArgs &a, int fmt, unsigned gx, unsigned gy, void *stream);
+int launch_render_e4(const KernelArgs &a, int fmt, unsigned gx, unsigned gy, void *stream);
+int launch_render_e56(int ext, const KernelArgs &a, int fmt, unsigned gx, unsigned gy, void *stream);
 int launch_detile(const void *tiles, void *frame, int w, int h, int tile_size, int tiles_x,
                   const int *tile_ids, int n_tiles, int pixel_format, void *stream);
 // The resolve of vx_render_aa (vx_resolve.hip): `rows` output rows of w pixels into dst from

@@ -1,7 +1,8 @@
 // vx_query.hip — batched ray queries (vx_query_rays): picking and place-label
 // visibility on the primary traversal's octant copies.  A translation unit of
 // its own: kernel_meta.check() budgets every kernel whose name holds k_render,
-// and this one shares nothing with them but the device helpers of vx_render.h.
+// and this one shares nothing with them but device helpers: the arithmetic
+// (vx_math.h), the byte converts and loads (vx_loads.h), ray_rcp (vx_walk.h).
 //
 // One lane per ray.  Per ray, exactly the oracle's primary_walk + walk(...,
 // glass_layer = 1, ...) (oracle/vxo_render.c) with the ray's own origin in the
@@ -21,7 +22,9 @@
 // of its bounds even for a NaN first operand) -- at most cap cells outside the
 // grid on any axis, and the border is pad = cap cells wide.  A border cell is
 // the sentinel and ends the walk; the iteration cap ends anything else.
-#include "vx_render.h"
+#include "vx_math.h"
+#include "vx_loads.h"
+#include "vx_walk.h"
 
 namespace vx {
 namespace {

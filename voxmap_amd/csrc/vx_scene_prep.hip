@@ -1,85 +1,179 @@
-// vx_kernels.hip — CDNA4 (gfx950) kernels of the Voxmap shading path besides
-// the 3D render kernel: the render dispatch (each EXT mode's launches live in
-// their own unit, vx_render_e*.hip), the 2D mode, the de-tile and stats
-// passes, and the per-scene field preparation (octant boxes, sun exit tables,
-// the greedy mesh per face, AO pairs, noise quads).
-#include "vx_render.h"
+// vx_scene_prep.hip — the once-per-scene field preparation on the GPU (gfx950),
+// in the order the scene build runs it (vx_api.cpp build_scene): vis colour and
+// 2D footprint, the sun and AO arrays, AO pairs and noise quads, prefix sums,
+// the octant cubes and boxes, the greedy mesh per face and its octant copies,
+// the sun exit, cone and doom tables (the last two per sun direction, built
+// when a frame first asks), then the read-back unpackers.  Nothing here is on
+// the per-frame path; nothing uses the render kernel's headers.
+#include <hip/hip_runtime.h>
+
+#include "vx_internal.h"
 
 namespace vx {
 namespace {
+// kernel k over n elements, one thread each, 256 to a block (every kernel
+// here that takes one tests its index against its own n)
+template <typename... P, typename... A>
+void launch_n(void (*k)(P...), size_t n, void *stream, A... args) {
+    hipLaunchKernelGGL(k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, args...);
+}
 
-// 2D mode frames (quality 0) in a kernel of their own: the 3D kernel keeps its
-// code and registers (a third user of the frame constants in k_render made
-// the compiler copy KernelArgs to scratch).  Same pixel mapping and stores.
-template <int FMT, bool STATS, bool TILED>
-__global__ __launch_bounds__(kWG) void k_render_2d(KernelArgs a) {
-    __shared__ uint32_t s_px[kBY][kBX];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lx = ((wave % kWX) << 3) | (lane & 7);
-    const int ly = ((wave / kWX) << 3) | (lane >> 3);
-    int ox, oy, tx0 = 0, ty0 = 0, tile_k = 0;
-    if (TILED) {
-        const int perx = a.tile_w >> kBXS, pery = a.tile_h >> kBYS;
-        const int bpt = perx * pery;
-        tile_k = blockIdx.x / bpt;
-        const int sub = blockIdx.x % bpt;
-        const int tid = a.tile_ids[tile_k];
-        tx0 = (sub % perx) << kBXS;
-        ty0 = (sub / perx) << kBYS;
-        ox = (tid % a.tiles_x) * a.tile_w + tx0;
-        oy = (tid / a.tiles_x) * a.tile_h + ty0;
-    } else {
-        ox = blockIdx.x << kBXS;
-        oy = blockIdx.y << kBYS;
-    }
-    const int px = ox + lx, py = oy + ly;
-    Counters cnt = {};
-    unsigned n_sky = 0, n_block = 0, n_glass = 0, n_px = 0;
-    if (px < a.w && py < a.h) {
-        float d0, d1, d2, rgba[4];
-        view_ray(a.fc, px, py, d0, d1, d2);
-        shade_2d(a, d0, d1, d2, rgba, cnt, n_sky, n_block, n_glass);
-        if (FMT == VX_PIXEL_RGBA8)
-            s_px[ly][lx] = pack_rgba8(rgba);
-        else
-            store_pixel<FMT>(a, out_index<TILED>(a, tile_k, tx0 + lx, ty0 + ly, px, py), rgba);
-        n_px = 1;
-    }
-    if (FMT == VX_PIXEL_RGBA8) {
-        __syncthreads();
-        const int sx = threadIdx.x & (kBX - 1), sy = threadIdx.x >> kBXS;
-        if (ox + sx < a.w && oy + sy < a.h)
-            reinterpret_cast<uint32_t *>(a.out)[out_index<TILED>(a, tile_k, tx0 + sx, ty0 + sy, ox + sx, oy + sy)] =
-                s_px[sy][sx];
-    }
-    if (STATS) {
-        unsigned long long v[ST_COUNT] = {};
-        v[ST_PIXELS] = wave_sum(n_px);
-        v[ST_SKY] = wave_sum(n_sky);
-        v[ST_BLOCK] = wave_sum(n_block);
-        v[ST_GLASS] = wave_sum(n_glass);
-        v[ST_PRIM_FETCH] = wave_sum(cnt.prim_fetch);
-        if (lane == 0) {
-            unsigned long long *row = a.stats + (size_t)((blockIdx.x + blockIdx.y * 7) & 63) * ST_COUNT;
-#pragma unroll
-            for (int i = 0; i < ST_COUNT; i++)
-                if (v[i]) atomicAdd(row + i, v[i]);
+// map.bin B -> the traversal's vis colour, in place in the linear upload (B
+// kept in bcol for vx_scene_read_field): the meshed palette indices 1..21
+// (sdf.cpp:284 meshes colours < pal_size = 22; render.vert:21) stay, anything
+// else -- air = pal_size (sdf.cpp:229-233, 466-468), 0, >= 22 -- is 0: never a surface
+__global__ void k_vis(uint32_t *lin, uint8_t *bcol, size_t N) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const uint32_t t = lin[i];
+    const uint32_t b = (t >> 16) & 0xffu;
+    bcol[i] = (uint8_t)b;
+    const uint32_t v = b - 1u < (uint32_t)(VX_PAL_SIZE - 1) ? b : 0u;
+    lin[i] = (t & 0xff00ffffu) | (v << 16);
+}
+// 2D mode footprint (sdf.cpp:201-204, 235-239): per column the vis colour of
+// the top block with z >= 1 (a block is R == 0, sdf.cpp:430), else 0
+__global__ void k_footprint(const uint32_t *lin, uint8_t *c2d, int X, int Y, int Z) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)X * Y) return;
+    uint8_t c = 0;
+    for (int z = Z - 1; z >= 1; z--) {
+        const uint32_t t = lin[i + (size_t)X * Y * z];
+        if ((t & 0xffu) == 0) {
+            c = (uint8_t)((t >> 16) & 0xffu);
+            break;
         }
     }
+    c2d[i] = c;
+}
+}  // namespace
+
+int launch_field_vis(uint32_t *lin, uint8_t *bcol, int X, int Y, int Z, void *stream) {
+    const size_t N = (size_t)X * Y * Z;
+    launch_n(k_vis, N, stream, lin, bcol, N);
+    return (int)hipGetLastError();
 }
 
-// Scatter compact tile-major pixels into a frame.
-template <typename T>
-__global__ void k_detile(const T *tiles, T *frame, int w, int h, int ts, int tiles_x, const int *ids, int n_tiles) {
+int launch_footprint(const uint32_t *lin, uint8_t *c2d, int X, int Y, int Z, void *stream) {
+    launch_n(k_footprint, (size_t)X * Y, stream, lin, c2d, X, Y, Z);
+    return (int)hipGetLastError();
+}
+
+namespace {
+// linear RGBA upload -> sun channel arrays and the AO array
+__global__ void k_pack_sun(const uint32_t *src, uint8_t *sun, uint16_t *rg, size_t N) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t per = (size_t)ts * ts;
-    if (i >= per * n_tiles) return;
-    const int k = (int)(i / per), r = (int)(i % per);
-    const int tid = ids[k];
-    const int x = (tid % tiles_x) * ts + r % ts, y = (tid / tiles_x) * ts + r / ts;
-    if (x >= 0 && y >= 0 && x < w && y < h) frame[(size_t)y * w + x] = tiles[i];
+    if (i >= N) return;
+    const uint32_t t = src[i];
+    sun[i] = (uint8_t)(t & 0xffu);
+    sun[N + i] = (uint8_t)((t >> 8) & 0xffu);
+    rg[i] = (uint16_t)(t & 0xffffu);
+}
+// linear RGBA upload -> the padded int8 sun channels (border pre-filled with -1)
+__global__ void k_sun_pad(const uint32_t *src, int8_t *sunp, int X, int Y, int Z, int SB) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)X * Y * Z) return;
+    const int x = (int)(i % X), y = (int)((i / X) % Y), z = (int)(i / ((size_t)X * Y));
+    const size_t Xp = (size_t)X + 2 * SB, Yp = (size_t)Y + 2 * SB, Zp = (size_t)Z + 2 * SB;
+    const size_t j = (size_t)(x + SB) + Xp * ((size_t)(y + SB) + Yp * (size_t)(z + SB));
+    const uint32_t t = src[i];
+    sunp[j] = (int8_t)(t & 0xffu);
+    sunp[Xp * Yp * Zp + j] = (int8_t)((t >> 8) & 0xffu);
+}
+}  // namespace
+
+int launch_field_pack(const uint32_t *lin, uint8_t *sun, uint16_t *rg, int X, int Y, int Z, void *stream) {
+    const size_t N = (size_t)X * Y * Z;
+    launch_n(k_pack_sun, N, stream, lin, sun, rg, N);
+    return (int)hipGetLastError();
 }
 
+int launch_sun_pad(const uint32_t *lin, int8_t *sunp, int X, int Y, int Z, int SB, void *stream) {
+    launch_n(k_sun_pad, (size_t)X * Y * Z, stream, lin, sunp, X, Y, Z, SB);
+    return (int)hipGetLastError();
+}
+
+namespace {
+// AO x-pairs (sdf_lin): entry (p, y, z), p = 0..X, = rg of cells clamp(p - 1) and clamp(p)
+__global__ void k_ao_pairs(const uint16_t *rg, uint32_t *rg2, int X, int Y, int Z) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t row = (size_t)X + 1;
+    if (i >= row * Y * Z) return;
+    const int p = (int)(i % row);
+    const size_t yz = i / row;
+    const int x0 = max(p - 1, 0), x1 = min(p, X - 1);
+    rg2[i] = (uint32_t)rg[yz * X + x0] | ((uint32_t)rg[yz * X + x1] << 16);
+}
+// noise quads: per texel (x, y), one u32 per channel plane holding that channel
+// of texels (x, y), (x+1, y), (x, y+1), (x+1, y+1) (W, H powers of two, REPEAT):
+// plane 0 = A (fbm), planes 1..3 = R, G, B (white)
+__global__ void k_noise_quads(const uint32_t *noise, uint32_t *q, int W, int H) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t n = (size_t)W * H;
+    if (i >= n) return;
+    const int x = (int)(i % W), y = (int)(i / W);
+    const int x1 = (x + 1) & (W - 1), y1 = (y + 1) & (H - 1);
+    const uint32_t t00 = noise[(size_t)y * W + x], t10 = noise[(size_t)y * W + x1];
+    const uint32_t t01 = noise[(size_t)y1 * W + x], t11 = noise[(size_t)y1 * W + x1];
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        const int sh = p == 0 ? 24 : 8 * (p - 1);
+        q[p * n + i] = ((t00 >> sh) & 0xffu) | (((t10 >> sh) & 0xffu) << 8) | (((t01 >> sh) & 0xffu) << 16) |
+                       (((t11 >> sh) & 0xffu) << 24);
+    }
+}
+}  // namespace
+
+int launch_ao_pairs(const uint16_t *rg, uint32_t *rg2, int X, int Y, int Z, void *stream) {
+    launch_n(k_ao_pairs, ((size_t)X + 1) * Y * Z, stream, rg, rg2, X, Y, Z);
+    return (int)hipGetLastError();
+}
+
+int launch_noise_quads(const uint32_t *noise, uint32_t *noise4, int W, int H, void *stream) {
+    launch_n(k_noise_quads, (size_t)W * H, stream, noise, noise4, W, H);
+    return (int)hipGetLastError();
+}
+
+namespace {
+// ---- prefix sums of solid (non-air) cells, S[(X+1)(Y+1)(Z+1)], S(0, ., .) =
+// S(., 0, .) = S(., ., 0) = 0: any box's solid count in 8 loads (k_oct_box)
+__device__ __forceinline__ size_t ps_index(int x, int y, int z, int X, int Y) {
+    return (size_t)x + (size_t)(X + 1) * ((size_t)y + (size_t)(Y + 1) * (size_t)z);
+}
+__global__ void k_psum_x(const uint32_t *lin, int *S, int X, int Y, int Z) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;     // (y, z) row of S
+    if (i >= (size_t)(Y + 1) * (Z + 1)) return;
+    const int y = (int)(i % (Y + 1)), z = (int)(i / (Y + 1));
+    int acc = 0;
+    S[ps_index(0, y, z, X, Y)] = 0;
+    for (int x = 1; x <= X; x++) {
+        if (y > 0 && z > 0)
+            acc += ((lin[(size_t)(x - 1) + (size_t)X * ((size_t)(y - 1) + (size_t)Y * (size_t)(z - 1))] >> 16) & 0xffu) != 0;
+        S[ps_index(x, y, z, X, Y)] = acc;
+    }
+}
+__global__ void k_psum_yz(int *S, int X, int Y, int Z, int axis) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;     // x fastest: coalesced
+    const int n = axis == 1 ? Y : Z, m = axis == 1 ? Z : Y;
+    if (i >= (size_t)(X + 1) * (m + 1)) return;
+    const int x = (int)(i % (X + 1)), j = (int)(i / (X + 1));
+    int acc = 0;
+    for (int k = 1; k <= n; k++) {
+        const size_t q = axis == 1 ? ps_index(x, k, j, X, Y) : ps_index(x, j, k, X, Y);
+        acc += S[q];
+        S[q] = acc;
+    }
+}
+}  // namespace
+
+int launch_field_psum(const uint32_t *lin, int *S, int X, int Y, int Z, void *stream) {
+    launch_n(k_psum_x, (size_t)(Y + 1) * (Z + 1), stream, lin, S, X, Y, Z);
+    launch_n(k_psum_yz, (size_t)(X + 1) * (Z + 1), stream, S, X, Y, Z, 1);
+    launch_n(k_psum_yz, (size_t)(X + 1) * (Y + 1), stream, S, X, Y, Z, 2);
+    return (int)hipGetLastError();
+}
+
+namespace {
 // ---- A channel of octant copy `oct`: size r of the air cube ahead of a cell
 // (oracle vxo_field_octant), separable one-sided passes:
 // L = min_dz max(dz, min_dy max(dy, min_dx dx)), dx, dy, dz in [0, cap) toward
@@ -115,100 +209,6 @@ __global__ void k_oct_yz(const uint8_t *gin, uint8_t *gout, uint32_t *field, int
     if (axis == 1) gout[i] = (uint8_t)best;
     else field[i] = (field[i] & 0x00ffffffu) | ((uint32_t)(best > 0 ? best - 1 : 0) << 24);
 }
-
-__global__ void k_reduce_stats(unsigned long long *stats) {
-    const int i = threadIdx.x;
-    if (i < ST_COUNT) {
-        unsigned long long s = 0;
-        for (int r = 0; r < 64; r++) s += stats[r * ST_COUNT + i];
-        stats[i] = s;
-    }
-}
-
-}  // namespace
-
-int launch_render(const KernelArgs &a, int fmt, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const bool tiled = a.tile_ids != nullptr;
-    const bool st = a.stats != nullptr;
-    dim3 block(kWG);
-    dim3 grid = tiled ? dim3(a.n_tiles * (a.tile_w >> kBXS) * (a.tile_h >> kBYS))
-                      : dim3((a.w + kBX - 1) / kBX, (a.h + kBY - 1) / kBY);
-    if (a.fc.quality == 0) {          // MODE_2D: the vertex2d mesh (render.js:278, 287)
-#define VX_L2(F, S, T) hipLaunchKernelGGL((k_render_2d<F, S, T>), grid, block, 0, s, a)
-#define VX_L2T(F, S) do { if (tiled) VX_L2(F, S, true); else VX_L2(F, S, false); } while (0)
-        if (fmt == VX_PIXEL_RGBA32F) { if (st) VX_L2T(0, true); else VX_L2T(0, false); }
-        else { if (st) VX_L2T(1, true); else VX_L2T(1, false); }
-#undef VX_L2T
-#undef VX_L2
-        if (st) hipLaunchKernelGGL(k_reduce_stats, dim3(1), dim3(64), 0, s, a.stats);
-        return (int)hipGetLastError();
-    }
-    const bool brick_ok = a.fc.soft_sg >= 0 && a.sunp && a.fc.soft_lg >= 4 && (a.SXp & 3) == 0 && a.SB >= 9;
-    // the general shading block (glass in draw order, REFLECT_ALL): EXT 5 / 6 (not with the pooled pass)
-    const bool general = (a.fc.flags & (VX_FLAG_GLASS_ORDER | VX_FLAG_REFLECT_ALL)) != 0;
-    const int ext = a.fc.n_sun > 1 ? (general ? 6 : (a.fc.flags & VX_FLAG_SOFT_BRICK) && brick_ok ? 4
-                                      : (a.fc.flags & (VX_FLAG_SOFT_POOL | VX_FLAG_SOFT_BRICK)) ? 3 : 2)
-                                   : (general ? 5 : (a.fc.flags & (VX_FLAG_REFLECT | VX_FLAG_ROUGH)) ? 1 : 0);
-    int rc;
-    switch (ext) {
-        case 0: rc = launch_render_e0(a, fmt, grid.x, grid.y, stream); break;
-        case 1: rc = launch_render_e1(a, fmt, grid.x, grid.y, stream); break;
-        case 2: rc = launch_render_e2(a, fmt, grid.x, grid.y, stream); break;
-        case 3: rc = launch_render_e3(a, fmt, grid.x, grid.y, stream); break;
-        case 4: rc = launch_render_e4(a, fmt, grid.x, grid.y, stream); break;
-        default: rc = launch_render_e56(ext, a, fmt, grid.x, grid.y, stream); break;
-    }
-    if (rc) return rc;
-    if (st) hipLaunchKernelGGL(k_reduce_stats, dim3(1), dim3(64), 0, s, a.stats);
-    return (int)hipGetLastError();
-}
-
-int launch_detile(const void *tiles, void *frame, int w, int h, int ts, int tiles_x, const int *ids,
-                  int n_tiles, int fmt, void *stream) {
-    const size_t n = (size_t)ts * ts * n_tiles;
-    dim3 grid((unsigned)((n + 255) / 256));
-    hipStream_t s = (hipStream_t)stream;
-    if (fmt == VX_PIXEL_RGBA32F)
-        hipLaunchKernelGGL(k_detile<float4>, grid, dim3(256), 0, s, (const float4 *)tiles, (float4 *)frame, w, h, ts,
-                           tiles_x, ids, n_tiles);
-    else
-        hipLaunchKernelGGL(k_detile<uint32_t>, grid, dim3(256), 0, s, (const uint32_t *)tiles, (uint32_t *)frame, w,
-                           h, ts, tiles_x, ids, n_tiles);
-    return (int)hipGetLastError();
-}
-
-namespace {
-// ---- prefix sums of solid (non-air) cells, S[(X+1)(Y+1)(Z+1)], S(0, ., .) =
-// S(., 0, .) = S(., ., 0) = 0: any box's solid count in 8 loads (k_oct_box)
-__device__ __forceinline__ size_t ps_index(int x, int y, int z, int X, int Y) {
-    return (size_t)x + (size_t)(X + 1) * ((size_t)y + (size_t)(Y + 1) * (size_t)z);
-}
-__global__ void k_psum_x(const uint32_t *lin, int *S, int X, int Y, int Z) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;     // (y, z) row of S
-    if (i >= (size_t)(Y + 1) * (Z + 1)) return;
-    const int y = (int)(i % (Y + 1)), z = (int)(i / (Y + 1));
-    int acc = 0;
-    S[ps_index(0, y, z, X, Y)] = 0;
-    for (int x = 1; x <= X; x++) {
-        if (y > 0 && z > 0)
-            acc += ((lin[(size_t)(x - 1) + (size_t)X * ((size_t)(y - 1) + (size_t)Y * (size_t)(z - 1))] >> 16) & 0xffu) != 0;
-        S[ps_index(x, y, z, X, Y)] = acc;
-    }
-}
-__global__ void k_psum_yz(int *S, int X, int Y, int Z, int axis) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;     // x fastest: coalesced
-    const int n = axis == 1 ? Y : Z, m = axis == 1 ? Z : Y;
-    if (i >= (size_t)(X + 1) * (m + 1)) return;
-    const int x = (int)(i % (X + 1)), j = (int)(i / (X + 1));
-    int acc = 0;
-    for (int k = 1; k <= n; k++) {
-        const size_t q = axis == 1 ? ps_index(x, k, j, X, Y) : ps_index(x, j, k, X, Y);
-        acc += S[q];
-        S[q] = acc;
-    }
-}
-
 // ---- one octant's prim copy: colour | ex << 8 | ey << 16 | ez << 24, the
 // cube r (A byte of the upload, k_oct_*) grown to the largest x extent, then
 // y, then z, each <= cap - 1, by bisection on box emptiness (oracle
@@ -256,6 +256,26 @@ __global__ void k_oct_box(const uint32_t *lin, const int *S, uint32_t *dst, int 
     dst[(size_t)(x + P) + Xp * ((size_t)(y + P) + Yp * (size_t)(z + P))] =
         col | ((uint32_t)e[0] << 8) | ((uint32_t)e[1] << 16) | ((uint32_t)e[2] << 24);
 }
+}  // namespace
+
+int launch_field_octant(uint32_t *field, int X, int Y, int Z, int cap, int oct, uint8_t *ga, uint8_t *gb,
+                        void *stream) {
+    const size_t N = (size_t)X * Y * Z;
+    const int sx = oct & 1 ? -1 : 1, sy = oct & 2 ? -1 : 1, sz = oct & 4 ? -1 : 1;
+    launch_n(k_oct_x, N, stream, field, ga, X, Y, Z, cap, sx);
+    launch_n(k_oct_yz, N, stream, ga, gb, field, X, Y, Z, cap, 1, sy);
+    launch_n(k_oct_yz, N, stream, gb, ga, field, X, Y, Z, cap, 2, sz);
+    return (int)hipGetLastError();
+}
+
+int launch_field_box(const uint32_t *lin, const int *S, uint32_t *prim_copy, int X, int Y, int Z, int pad, int cap,
+                     int oct, void *stream) {
+    const int sx = oct & 1 ? -1 : 1, sy = oct & 2 ? -1 : 1, sz = oct & 4 ? -1 : 1;
+    launch_n(k_oct_box, (size_t)X * Y * Z, stream, lin, S, prim_copy, X, Y, Z, pad, cap, sx, sy, sz);
+    return (int)hipGetLastError();
+}
+
+namespace {
 // ---- the greedy mesh per face (sdf.cpp:281-356; oracle vxo_face_quads): for
 // every face the mesh has, its offset du | dv << 8 from the origin of the quad
 // covering it, along u = (d+1)%3, v = (d+2)%3 -- the v_cellPos / v_fractPos
@@ -354,80 +374,30 @@ __global__ void k_qcopy(const uint16_t *qf, uint32_t *dst, int X, int Y, int Z, 
     const size_t Xp = (size_t)X + 2 * P, Yp = (size_t)Y + 2 * P;
     dst[(size_t)(x + P) + Xp * ((size_t)(y + P) + Yp * (size_t)(z + P))] = w;
 }
-// the table in the oracle's layout (6 per cell) for vx_scene_read_face_quads
-__global__ void k_face_quads_interleave(const uint16_t *qf, uint16_t *out, size_t N) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= 6 * N) return;
-    out[i] = qf[(i % 6) * N + i / 6];
+}  // namespace
+
+int launch_face_quads(const uint32_t *lin, uint16_t *qface, int X, int Y, int Z, int chunk, void *stream) {
+    const size_t N = (size_t)X * Y * Z;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(qface, 0xFF, 12 * N, s);
+    if (e != hipSuccess) return (int)e;
+    const int ncx = (X + chunk - 1) / chunk, ncy = (Y + chunk - 1) / chunk, ncz = (Z + chunk - 1) / chunk;
+    const size_t blocks = (size_t)ncx * ncy * ncz * 6 * chunk;
+    if (blocks >= (1ull << 31)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_face_quads, dim3((unsigned)blocks), dim3(64), (size_t)chunk * chunk, s, lin, qface, X, Y, Z,
+                       chunk, ncy, ncz, N);
+    return (int)hipGetLastError();
 }
-// AO x-pairs (sdf_lin): entry (p, y, z), p = 0..X, = rg of cells clamp(p - 1) and clamp(p)
-__global__ void k_ao_pairs(const uint16_t *rg, uint32_t *rg2, int X, int Y, int Z) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t row = (size_t)X + 1;
-    if (i >= row * Y * Z) return;
-    const int p = (int)(i % row);
-    const size_t yz = i / row;
-    const int x0 = max(p - 1, 0), x1 = min(p, X - 1);
-    rg2[i] = (uint32_t)rg[yz * X + x0] | ((uint32_t)rg[yz * X + x1] << 16);
+
+int launch_qcopy(const uint16_t *qface, uint32_t *qcopy, int X, int Y, int Z, int pad, size_t texels, void *stream) {
+    const size_t N = (size_t)X * Y * Z;
+    hipError_t e = hipMemsetAsync(qcopy, 0, 8 * texels * 4, (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    for (int o = 0; o < 8; o++) launch_n(k_qcopy, N, stream, qface, qcopy + o * texels, X, Y, Z, pad, o, N);
+    return (int)hipGetLastError();
 }
-// noise quads: per texel (x, y), one u32 per channel plane holding that channel
-// of texels (x, y), (x+1, y), (x, y+1), (x+1, y+1) (W, H powers of two, REPEAT):
-// plane 0 = A (fbm), planes 1..3 = R, G, B (white)
-__global__ void k_noise_quads(const uint32_t *noise, uint32_t *q, int W, int H) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t n = (size_t)W * H;
-    if (i >= n) return;
-    const int x = (int)(i % W), y = (int)(i / W);
-    const int x1 = (x + 1) & (W - 1), y1 = (y + 1) & (H - 1);
-    const uint32_t t00 = noise[(size_t)y * W + x], t10 = noise[(size_t)y * W + x1];
-    const uint32_t t01 = noise[(size_t)y1 * W + x], t11 = noise[(size_t)y1 * W + x1];
-#pragma unroll
-    for (int p = 0; p < 4; p++) {
-        const int sh = p == 0 ? 24 : 8 * (p - 1);
-        q[p * n + i] = ((t00 >> sh) & 0xffu) | (((t10 >> sh) & 0xffu) << 8) | (((t01 >> sh) & 0xffu) << 16) |
-                       (((t11 >> sh) & 0xffu) << 24);
-    }
-}
-// linear RGBA upload -> sun channel arrays and the AO array
-__global__ void k_pack_sun(const uint32_t *src, uint8_t *sun, uint16_t *rg, size_t N) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    const uint32_t t = src[i];
-    sun[i] = (uint8_t)(t & 0xffu);
-    sun[N + i] = (uint8_t)((t >> 8) & 0xffu);
-    rg[i] = (uint16_t)(t & 0xffffu);
-}
-// linear RGBA upload -> the padded int8 sun channels (border pre-filled with -1)
-__global__ void k_sun_pad(const uint32_t *src, int8_t *sunp, int X, int Y, int Z, int SB) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)X * Y * Z) return;
-    const int x = (int)(i % X), y = (int)((i / X) % Y), z = (int)(i / ((size_t)X * Y));
-    const size_t Xp = (size_t)X + 2 * SB, Yp = (size_t)Y + 2 * SB, Zp = (size_t)Z + 2 * SB;
-    const size_t j = (size_t)(x + SB) + Xp * ((size_t)(y + SB) + Yp * (size_t)(z + SB));
-    const uint32_t t = src[i];
-    sunp[j] = (int8_t)(t & 0xffu);
-    sunp[Xp * Yp * Zp + j] = (int8_t)((t >> 8) & 0xffu);
-}
-// ---- first-step bits of an exit copy (DESIGN.md §3 "Sun exit tables", the
-// first step).  A marked cell c (value < 0) gets bit a (a = face axis) when
-// the 2 x 2 block c + {0, s_j} x {0, s_k} of the two other axes is marked
-// too: the value becomes -1 - bits (-1 .. -8; every negative value is the
-// march's exit).  k_render reads the bits at a fragment's air cell: a first
-// step from the face lands in that block, so the march can end before it.
-__global__ void k_exit_face_bits(int8_t *cp, int X, int Y, int Z, int SB, int SXp, size_t SXpYp, int sx, int sy,
-                                 int sz) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)X * Y * Z) return;
-    const int x = (int)(i % X), y = (int)((i / X) % Y), z = (int)(i / ((size_t)X * Y));
-    const size_t p = (size_t)(x + SB) + (size_t)SXp * (size_t)(y + SB) + SXpYp * (size_t)(z + SB);
-    if (cp[p] >= 0) return;
-    const ptrdiff_t dx = sx, dy = (ptrdiff_t)sy * SXp, dz = (ptrdiff_t)sz * (ptrdiff_t)SXpYp;
-    auto m = [&](ptrdiff_t o) { return cp[p + o] < 0; };      // marked (any negative value, border included)
-    const int bx = m(dy) && m(dz) && m(dy + dz);
-    const int by = m(dx) && m(dz) && m(dx + dz);
-    const int bz = m(dx) && m(dy) && m(dx + dy);
-    cp[p] = (int8_t)(-1 - (bx | (by << 1) | (bz << 2)));
-}
+
+namespace {
 // ---- orthant-exit march copies (DESIGN.md §3 "Orthant exit").  For ray
 // octant o (bit i: r_i > 0) and its channel (R if r_z > 0, else G), a cell
 // whose orthant ahead -- every cell c' with c'_i >= c_i on a positive axis,
@@ -473,6 +443,43 @@ __global__ void k_ox_z(const int8_t *ch, const uint8_t *fl, int8_t *out, int X, 
         out[p] = acc ? ch[p] : (int8_t)-1;
     }
 }
+// ---- first-step bits of an exit copy (DESIGN.md §3 "Sun exit tables", the
+// first step).  A marked cell c (value < 0) gets bit a (a = face axis) when
+// the 2 x 2 block c + {0, s_j} x {0, s_k} of the two other axes is marked
+// too: the value becomes -1 - bits (-1 .. -8; every negative value is the
+// march's exit).  k_render reads the bits at a fragment's air cell: a first
+// step from the face lands in that block, so the march can end before it.
+__global__ void k_exit_face_bits(int8_t *cp, int X, int Y, int Z, int SB, int SXp, size_t SXpYp, int sx, int sy,
+                                 int sz) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)X * Y * Z) return;
+    const int x = (int)(i % X), y = (int)((i / X) % Y), z = (int)(i / ((size_t)X * Y));
+    const size_t p = (size_t)(x + SB) + (size_t)SXp * (size_t)(y + SB) + SXpYp * (size_t)(z + SB);
+    if (cp[p] >= 0) return;
+    const ptrdiff_t dx = sx, dy = (ptrdiff_t)sy * SXp, dz = (ptrdiff_t)sz * (ptrdiff_t)SXpYp;
+    auto m = [&](ptrdiff_t o) { return cp[p + o] < 0; };      // marked (any negative value, border included)
+    const int bx = m(dy) && m(dz) && m(dy + dz);
+    const int by = m(dx) && m(dz) && m(dx + dz);
+    const int bz = m(dx) && m(dy) && m(dx + dy);
+    cp[p] = (int8_t)(-1 - (bx | (by << 1) | (bz << 2)));
+}
+}  // namespace
+
+int launch_sun_exit(const int8_t *sunp, int8_t *sunx, uint8_t *flags, int X, int Y, int Z, int SB, void *stream) {
+    const int SXp = X + 2 * SB, SYp = Y + 2 * SB, SZp = Z + 2 * SB;
+    const size_t SXpYp = (size_t)SXp * SYp, np = SXpYp * SZp;
+    for (int o = 0; o < 8; o++) {
+        const int sx = o & 1 ? 1 : -1, sy = o & 2 ? 1 : -1, sz = o & 4 ? 1 : -1;
+        const int8_t *ch = sz > 0 ? sunp : sunp + np;          // R for up-going rays, G otherwise
+        launch_n(k_ox_x, (size_t)Y * Z, stream, ch, flags, X, Y, Z, SB, SXp, SXpYp, sx);
+        launch_n(k_ox_y, (size_t)X * Z, stream, flags, X, Y, Z, sy);
+        launch_n(k_ox_z, (size_t)X * Y, stream, ch, flags, sunx + o * np, X, Y, Z, SB, SXp, SXpYp, sz);
+        launch_n(k_exit_face_bits, (size_t)X * Y * Z, stream, sunx + o * np, X, Y, Z, SB, SXp, SXpYp, sx, sy, sz);
+    }
+    return (int)hipGetLastError();
+}
+
+namespace {
 // One layer z of a cone copy (oracle vxo_field_exit with a finite window):
 // D(x, y, z) = AND over i <= kx, j <= ky of [T(x', y', z) != 0 and
 // D(x', y', z + 1)], x' = x + i*sx, y' = y + j*sy; the channel's and the
@@ -622,164 +629,17 @@ __global__ void __launch_bounds__(256) k_doom_layer(const int8_t *sunp, size_t n
         }
     }
 }
-// map.bin B -> the traversal's vis colour, in place in the linear upload (B
-// kept in bcol for vx_scene_read_field): the meshed palette indices 1..21
-// (sdf.cpp:284 meshes colours < pal_size = 22; render.vert:21) stay, anything
-// else -- air = pal_size (sdf.cpp:229-233, 466-468), 0, >= 22 -- is 0: never a surface
-__global__ void k_vis(uint32_t *lin, uint8_t *bcol, size_t N) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    const uint32_t t = lin[i];
-    const uint32_t b = (t >> 16) & 0xffu;
-    bcol[i] = (uint8_t)b;
-    const uint32_t v = b - 1u < (uint32_t)(VX_PAL_SIZE - 1) ? b : 0u;
-    lin[i] = (t & 0xff00ffffu) | (v << 16);
-}
-// 2D mode footprint (sdf.cpp:201-204, 235-239): per column the vis colour of
-// the top block with z >= 1 (a block is R == 0, sdf.cpp:430), else 0
-__global__ void k_footprint(const uint32_t *lin, uint8_t *c2d, int X, int Y, int Z) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)X * Y) return;
-    uint8_t c = 0;
-    for (int z = Z - 1; z >= 1; z--) {
-        const uint32_t t = lin[i + (size_t)X * Y * z];
-        if ((t & 0xffu) == 0) {
-            c = (uint8_t)((t >> 16) & 0xffu);
-            break;
-        }
-    }
-    c2d[i] = c;
-}
-// One octant copy, linear: RGBA (R, G from rg; B = map.bin's B from bcol; A =
-// the cube size = min(ex, ey, ez), since the box grows from the largest cube)
-// for vx_scene_read_field_copy, or the raw texels (rg == nullptr: vis colour,
-// ex, ey, ez) for vx_scene_read_boxes
-__global__ void k_unpack(const uint16_t *rg, const uint8_t *bcol, const uint32_t *prim, uint32_t *dst, int X, int Y,
-                         int Z, int P) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)X * Y * Z) return;
-    const int x = (int)(i % X), y = (int)((i / X) % Y), z = (int)(i / ((size_t)X * Y));
-    const size_t Xp = (size_t)X + 2 * P, Yp = (size_t)Y + 2 * P;
-    const uint32_t p = prim[(size_t)(x + P) + Xp * ((size_t)(y + P) + Yp * (size_t)(z + P))];
-    if (!rg) {
-        dst[i] = p;
-        return;
-    }
-    const uint32_t e0 = (p >> 8) & 0xffu, e1 = (p >> 16) & 0xffu, e2 = p >> 24;
-    const uint32_t r = min(e0, min(e1, e2));
-    dst[i] = (uint32_t)rg[i] | ((uint32_t)bcol[i] << 16) | (r << 24);
-}
 }  // namespace
-
-int launch_ao_pairs(const uint16_t *rg, uint32_t *rg2, int X, int Y, int Z, void *stream) {
-    const size_t N = ((size_t)X + 1) * Y * Z;
-    hipLaunchKernelGGL(k_ao_pairs, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rg, rg2, X, Y,
-                       Z);
-    return (int)hipGetLastError();
-}
-
-int launch_face_quads(const uint32_t *lin, uint16_t *qface, int X, int Y, int Z, int chunk, void *stream) {
-    const size_t N = (size_t)X * Y * Z;
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(qface, 0xFF, 12 * N, s);
-    if (e != hipSuccess) return (int)e;
-    const int ncx = (X + chunk - 1) / chunk, ncy = (Y + chunk - 1) / chunk, ncz = (Z + chunk - 1) / chunk;
-    const size_t blocks = (size_t)ncx * ncy * ncz * 6 * chunk;
-    if (blocks >= (1ull << 31)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_face_quads, dim3((unsigned)blocks), dim3(64), (size_t)chunk * chunk, s, lin, qface, X, Y, Z,
-                       chunk, ncy, ncz, N);
-    return (int)hipGetLastError();
-}
-
-int launch_qcopy(const uint16_t *qface, uint32_t *qcopy, int X, int Y, int Z, int pad, size_t texels, void *stream) {
-    const size_t N = (size_t)X * Y * Z;
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(qcopy, 0, 8 * texels * 4, s);
-    if (e != hipSuccess) return (int)e;
-    for (int o = 0; o < 8; o++)
-        hipLaunchKernelGGL(k_qcopy, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, qface, qcopy + o * texels, X,
-                           Y, Z, pad, o, N);
-    return (int)hipGetLastError();
-}
-
-int launch_face_quads_interleave(const uint16_t *qface, uint16_t *out, size_t N, void *stream) {
-    hipLaunchKernelGGL(k_face_quads_interleave, dim3((unsigned)((6 * N + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, qface, out, N);
-    return (int)hipGetLastError();
-}
-
-int launch_noise_quads(const uint32_t *noise, uint32_t *noise4, int W, int H, void *stream) {
-    const size_t N = (size_t)W * H;
-    hipLaunchKernelGGL(k_noise_quads, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, noise,
-                       noise4, W, H);
-    return (int)hipGetLastError();
-}
-
-int launch_field_pack(const uint32_t *lin, uint8_t *sun, uint16_t *rg, int X, int Y, int Z, void *stream) {
-    const size_t N = (size_t)X * Y * Z;
-    const dim3 grid((unsigned)((N + 255) / 256)), block(256);
-    hipLaunchKernelGGL(k_pack_sun, grid, block, 0, (hipStream_t)stream, lin, sun, rg, N);
-    return (int)hipGetLastError();
-}
-
-int launch_field_psum(const uint32_t *lin, int *S, int X, int Y, int Z, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const size_t nx = (size_t)(Y + 1) * (Z + 1), ny = (size_t)(X + 1) * (Z + 1), nz = (size_t)(X + 1) * (Y + 1);
-    hipLaunchKernelGGL(k_psum_x, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, lin, S, X, Y, Z);
-    hipLaunchKernelGGL(k_psum_yz, dim3((unsigned)((ny + 255) / 256)), dim3(256), 0, s, S, X, Y, Z, 1);
-    hipLaunchKernelGGL(k_psum_yz, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, S, X, Y, Z, 2);
-    return (int)hipGetLastError();
-}
-
-int launch_field_box(const uint32_t *lin, const int *S, uint32_t *prim_copy, int X, int Y, int Z, int pad, int cap,
-                     int oct, void *stream) {
-    const size_t N = (size_t)X * Y * Z;
-    const int sx = oct & 1 ? -1 : 1, sy = oct & 2 ? -1 : 1, sz = oct & 4 ? -1 : 1;
-    hipLaunchKernelGGL(k_oct_box, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lin, S,
-                       prim_copy, X, Y, Z, pad, cap, sx, sy, sz);
-    return (int)hipGetLastError();
-}
-
-int launch_sun_pad(const uint32_t *lin, int8_t *sunp, int X, int Y, int Z, int SB, void *stream) {
-    const size_t N = (size_t)X * Y * Z;
-    hipLaunchKernelGGL(k_sun_pad, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lin, sunp, X, Y,
-                       Z, SB);
-    return (int)hipGetLastError();
-}
-
-int launch_sun_exit(const int8_t *sunp, int8_t *sunx, uint8_t *flags, int X, int Y, int Z, int SB, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const int SXp = X + 2 * SB, SYp = Y + 2 * SB, SZp = Z + 2 * SB;
-    const size_t SXpYp = (size_t)SXp * SYp, np = SXpYp * SZp;
-    const size_t nx = (size_t)Y * Z, ny = (size_t)X * Z, nz = (size_t)X * Y;
-    for (int o = 0; o < 8; o++) {
-        const int sx = o & 1 ? 1 : -1, sy = o & 2 ? 1 : -1, sz = o & 4 ? 1 : -1;
-        const int8_t *ch = sz > 0 ? sunp : sunp + np;          // R for up-going rays, G otherwise
-        hipLaunchKernelGGL(k_ox_x, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, ch, flags, X, Y, Z, SB, SXp,
-                           SXpYp, sx);
-        hipLaunchKernelGGL(k_ox_y, dim3((unsigned)((ny + 255) / 256)), dim3(256), 0, s, flags, X, Y, Z, sy);
-        hipLaunchKernelGGL(k_ox_z, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, ch, flags, sunx + o * np, X,
-                           Y, Z, SB, SXp, SXpYp, sz);
-        const size_t n = (size_t)X * Y * Z;
-        hipLaunchKernelGGL(k_exit_face_bits, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sunx + o * np, X, Y,
-                           Z, SB, SXp, SXpYp, sx, sy, sz);
-    }
-    return (int)hipGetLastError();
-}
 
 int launch_sun_cone(const int8_t *sunp, int8_t *sunc, int X, int Y, int Z, int SB, int oct, int kx, int ky,
                     void *stream) {
     if (!(oct & 4) || kx < 0 || ky < 0 || kx > SB || ky > SB) return (int)hipErrorInvalidValue;
-    hipStream_t s = (hipStream_t)stream;
     const int SXp = X + 2 * SB, SYp = Y + 2 * SB;
     const size_t SXpYp = (size_t)SXp * SYp, n = (size_t)X * Y;
     const int sx = oct & 1 ? 1 : -1, sy = oct & 2 ? 1 : -1;
     for (int z = Z - 1; z >= 0; z--)          // R channel (up-going rays), top layer first
-        hipLaunchKernelGGL(k_sun_cone_layer, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sunp, sunc, X, Y, z,
-                           SB, SXp, SXpYp, sx, sy, kx, ky);
-    const size_t nc = n * Z;
-    hipLaunchKernelGGL(k_exit_face_bits, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, sunc, X, Y, Z, SB, SXp,
-                       SXpYp, sx, sy, 1);
+        launch_n(k_sun_cone_layer, n, stream, sunp, sunc, X, Y, z, SB, SXp, SXpYp, sx, sy, kx, ky);
+    launch_n(k_exit_face_bits, n * Z, stream, sunc, X, Y, Z, SB, SXp, SXpYp, sx, sy, 1);
     return (int)hipGetLastError();
 }
 
@@ -809,36 +669,42 @@ int launch_sun_doom(const int8_t *sunp, int8_t *sunc, int X, int Y, int Z, int S
     return (int)(e != hipSuccess ? e : f);
 }
 
+namespace {
+// the table in the oracle's layout (6 per cell) for vx_scene_read_face_quads
+__global__ void k_face_quads_interleave(const uint16_t *qf, uint16_t *out, size_t N) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 6 * N) return;
+    out[i] = qf[(i % 6) * N + i / 6];
+}
+// One octant copy, linear: RGBA (R, G from rg; B = map.bin's B from bcol; A =
+// the cube size = min(ex, ey, ez), since the box grows from the largest cube)
+// for vx_scene_read_field_copy, or the raw texels (rg == nullptr: vis colour,
+// ex, ey, ez) for vx_scene_read_boxes
+__global__ void k_unpack(const uint16_t *rg, const uint8_t *bcol, const uint32_t *prim, uint32_t *dst, int X, int Y,
+                         int Z, int P) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)X * Y * Z) return;
+    const int x = (int)(i % X), y = (int)((i / X) % Y), z = (int)(i / ((size_t)X * Y));
+    const size_t Xp = (size_t)X + 2 * P, Yp = (size_t)Y + 2 * P;
+    const uint32_t p = prim[(size_t)(x + P) + Xp * ((size_t)(y + P) + Yp * (size_t)(z + P))];
+    if (!rg) {
+        dst[i] = p;
+        return;
+    }
+    const uint32_t e0 = (p >> 8) & 0xffu, e1 = (p >> 16) & 0xffu, e2 = p >> 24;
+    const uint32_t r = min(e0, min(e1, e2));
+    dst[i] = (uint32_t)rg[i] | ((uint32_t)bcol[i] << 16) | (r << 24);
+}
+}  // namespace
+
+int launch_face_quads_interleave(const uint16_t *qface, uint16_t *out, size_t N, void *stream) {
+    launch_n(k_face_quads_interleave, 6 * N, stream, qface, out, N);
+    return (int)hipGetLastError();
+}
+
 int launch_field_unpack(const uint16_t *rg, const uint8_t *bcol, const uint32_t *prim_copy, uint32_t *out, int X,
                         int Y, int Z, int pad, void *stream) {
-    const size_t N = (size_t)X * Y * Z;
-    hipLaunchKernelGGL(k_unpack, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rg, bcol,
-                       prim_copy, out, X, Y, Z, pad);
-    return (int)hipGetLastError();
-}
-
-int launch_footprint(const uint32_t *lin, uint8_t *c2d, int X, int Y, int Z, void *stream) {
-    const size_t N = (size_t)X * Y;
-    hipLaunchKernelGGL(k_footprint, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lin, c2d,
-                       X, Y, Z);
-    return (int)hipGetLastError();
-}
-
-int launch_field_vis(uint32_t *lin, uint8_t *bcol, int X, int Y, int Z, void *stream) {
-    const size_t N = (size_t)X * Y * Z;
-    hipLaunchKernelGGL(k_vis, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lin, bcol, N);
-    return (int)hipGetLastError();
-}
-
-int launch_field_octant(uint32_t *field, int X, int Y, int Z, int cap, int oct, uint8_t *ga, uint8_t *gb,
-                        void *stream) {
-    const size_t N = (size_t)X * Y * Z;
-    dim3 grid((unsigned)((N + 255) / 256)), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    const int sx = oct & 1 ? -1 : 1, sy = oct & 2 ? -1 : 1, sz = oct & 4 ? -1 : 1;
-    hipLaunchKernelGGL(k_oct_x, grid, block, 0, s, (const uint32_t *)field, ga, X, Y, Z, cap, sx);
-    hipLaunchKernelGGL(k_oct_yz, grid, block, 0, s, ga, gb, field, X, Y, Z, cap, 1, sy);
-    hipLaunchKernelGGL(k_oct_yz, grid, block, 0, s, gb, ga, field, X, Y, Z, cap, 2, sz);
+    launch_n(k_unpack, (size_t)X * Y * Z, stream, rg, bcol, prim_copy, out, X, Y, Z, pad);
     return (int)hipGetLastError();
 }
 

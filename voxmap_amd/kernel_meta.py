@@ -112,7 +112,7 @@ def descriptor_modes(lib: str) -> dict[str, dict[str, int]]:
     """{mangled kernel name: {"dx10_clamp": 0/1, "ieee_mode": 0/1}} from the kernel
     descriptors (the ``<kernel>.kd`` objects in .rodata, which llvm-objdump prints
     as .amdhsa_* directives).  DX10_CLAMP is what makes the clamp output modifier
-    take a NaN to 0: vx_render.h's clamp01 relies on it."""
+    take a NaN to 0: vx_math.h's clamp01 relies on it."""
     out: dict[str, dict[str, int]] = {}
     with tempfile.TemporaryDirectory() as d:
         for co in code_objects(lib, d):
@@ -216,7 +216,7 @@ def check(lib: str) -> dict[str, dict[str, int]]:
         general = p is not None and p[3] >= 5
         if not stats and v.get("vgpr_count", 0) > (80 if brick else GENERAL_VGPR_LIMIT if general else RENDER_VGPR_LIMIT):
             bad.append(f"{name}: {v['vgpr_count']} VGPRs > {RENDER_VGPR_LIMIT}")
-    # clamp01 (vx_render.h) relies on the clamp modifier taking a NaN to 0
+    # clamp01 (vx_math.h) relies on the clamp modifier taking a NaN to 0
     modes = descriptor_modes(lib)
     for name in render:
         if modes.get(name, {}).get("dx10_clamp") != 1:
