@@ -43,11 +43,6 @@ def resolve_f32(hi: np.ndarray, s: int) -> np.ndarray:
     return out if s == 2 else _resolve2_f32(out)
 
 
-def quantise(ref: np.ndarray) -> np.ndarray:
-    """The RGBA8 frame of an fp32 oracle frame, as tests/test_shapes_gpu.py quantises it."""
-    return (np.clip(ref, 0, 1) * np.float32(255) + np.float32(0.5)).astype(np.uint8)
-
-
 def _slow_u8(hi, s):
     h, w = hi.shape[0] // s, hi.shape[1] // s
     out = np.zeros((h, w, 4), np.uint8)

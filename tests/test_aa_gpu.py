@@ -5,7 +5,7 @@ The sub-pixel rays of a w x h frame at factor s are the pixel rays of the
 the reference of a case is Oracle.render(params, s*w, s*h) (fp32), put through
 the numpy restatement of the header's resolve that tests/test_aa.py holds to a
 per-pixel loop -- bit for bit in RGBA32F, and in RGBA8 every byte of the oracle
-frame quantised as tests/test_shapes_gpu.py does and then integer-resolved.
+frame quantised (gpu_rig.quantise_rgba8) and then integer-resolved.
 
 Two scenes, one camera each (an eye and a view direction; the basis is built in
 look_frame) whose hi-res frames hold sky, block and glass pixels, asserted on
@@ -23,7 +23,9 @@ import threading
 import numpy as np
 import pytest
 
-from test_aa import BPP, F32, U8, quantise, resolve_f32, resolve_u8
+from gpu_rig import (Rig, assert_bytes_equal, assert_counters_equal, assert_no_cap_hits, assert_words_equal,
+                     gpu_available, quantise_rgba8)
+from test_aa import BPP, F32, U8, resolve_f32, resolve_u8
 from test_poses import frame_from_basis
 
 pytestmark = pytest.mark.gpu
@@ -39,14 +41,6 @@ CAMERAS = {
 TAN = 0.7                            # half-width of the view at distance 1
 
 
-def _torch_gpu():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:  # pragma: no cover
-        return False
-
-
 def look_frame(name, w, h, **kw):
     """The scene's camera at w x h: fwd the unit view direction, right horizontal, up
     perpendicular to both, the view TAN wide and TAN * h / w high whatever the size."""
@@ -60,22 +54,18 @@ def look_frame(name, w, h, **kw):
     return frame_from_basis(cell, fract, fwd, right * TAN, up * (TAN * h / w), w, h, **kw)
 
 
-class World:
+class World(Rig):
     """One scene on the device, the oracle over its read-back field, and the
     oracle's hi-res frames, each rendered once and left unchanged."""
 
     def __init__(self, name, noise):
-        import oracle
         import voxmap_amd as vx
         from voxmap_amd import scenes
         self.name = name
         grid = scenes.small_proc(3) if name == "proc3" else scenes.glass_wall()
         Z, Y, X = grid.shape
         assert (X, Y, Z) == ((96, 48, 16) if name == "proc3" else (64, 64, 16))
-        field = vx.field_build(grid)
-        self.scene = vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                              noise_format=vx.FORMAT_BIN, dims=(X, Y, Z), device=0)
-        self.oracle = oracle.Oracle(self.scene.read_field(), noise, exit=True)
+        super().__init__(vx.field_build(grid), noise, (X, Y, Z))
         self._hi = {}
 
     def hi(self, fr, s):
@@ -90,7 +80,7 @@ class World:
 
     def reference(self, fr, s, fmt):
         ref, ost = self.hi(fr, s)
-        return (resolve_f32(ref, s) if fmt == F32 else resolve_u8(quantise(ref), s)), ost
+        return (resolve_f32(ref, s) if fmt == F32 else resolve_u8(quantise_rgba8(ref), s)), ost
 
     def plain_stats(self, fr, s, fmt):
         """The counters of a plain Scene.render of the hi-res frame."""
@@ -104,11 +94,11 @@ _worlds = {}
 
 @pytest.fixture(scope="module", autouse=True)
 def _scenes(built):
-    if not _torch_gpu():
+    if not gpu_available():
         pytest.skip("no GPU visible")
     yield
     for w in _worlds.values():
-        w.scene.close()
+        w.close()
     _worlds.clear()
 
 
@@ -118,29 +108,18 @@ def world(name, noise):
     return _worlds[name]
 
 
-def _same(got, want, fmt):
-    if fmt == F32:
-        bad = got.view(np.uint32) != want.view(np.uint32)
-    else:
-        bad = got != want
-    assert not bad.any(), f"{int(bad.sum())} differ; first at {np.argwhere(bad)[:5].tolist()}"
-
-
 def _check(wd, fr, s, fmt, **kw):
     """render_aa with stats against the resolved oracle frame, the oracle's counters and
     the plain hi-res render's; returns the image."""
     want, ost = wd.reference(fr, s, fmt)
     img, st = wd.scene.render_aa(fr, s, pixel_format=fmt, stats=True, **kw)
     assert img.shape == (fr.height, fr.width, 4)
-    _same(img, want, fmt)
+    (assert_words_equal if fmt == F32 else assert_bytes_equal)(img, want)
     g = st.as_dict()
-    for k, v in ost.items():
-        assert g[k] == v, (k, g[k], v)
-    plain = wd.plain_stats(fr, s, fmt)
-    for k in plain:
-        if k != "kernel_ms":
-            assert g[k] == plain[k], (k, g[k], plain[k])
-    assert g["pixels"] == s * s * fr.width * fr.height and g["primary_cap_hits"] == 0
+    assert_counters_equal(g, ost)
+    assert_counters_equal(g, wd.plain_stats(fr, s, fmt))
+    assert_no_cap_hits(g)
+    assert g["pixels"] == s * s * fr.width * fr.height
     assert g["kernel_ms"] > 0
     return img
 
@@ -200,8 +179,7 @@ def test_factor_one_is_vx_render(fmt, noise):
     a, sa = wd.scene.render_aa(fr, 1, pixel_format=fmt, stats=True, scratch_cap=1)     # the cap is not looked at
     b, sb = wd.scene.render(fr, pixel_format=fmt, stats=True)
     assert a.tobytes() == b.tobytes()
-    da, db = sa.as_dict(), sb.as_dict()
-    assert {k: v for k, v in da.items() if k != "kernel_ms"} == {k: v for k, v in db.items() if k != "kernel_ms"}
+    assert_counters_equal(sa, sb)                   # two Stats: the same counters on both sides
 
 
 @pytest.mark.parametrize("shape,s,fmt,guard", [((37, 19), 2, U8, 64), ((37, 19), 4, F32, 64), ((64, 40), 2, U8, 64),

@@ -8,22 +8,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_rig import need_gpu  # noqa: F401 (an autouse fixture)
+
 pytestmark = pytest.mark.gpu
 
 X, Y, Z = 8, 8, 4
 W = H = 64
 N = X * Y * Z
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu(built):
-    try:
-        import torch
-        ok = torch.cuda.is_available()
-    except Exception:  # pragma: no cover
-        ok = False
-    if not ok:
-        pytest.skip("no GPU visible")
 
 
 def _grid():

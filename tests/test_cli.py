@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from gpu_rig import gpu_available
 from voxmap_amd import _abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,8 +30,7 @@ def test_cli_help_and_errors(built):
 @pytest.mark.gpu
 @pytest.mark.parametrize("source", ["grid", "blob", "blob_air0"])
 def test_cli_frame_equals_python_host(built, tmp_path, source):
-    import torch
-    if not torch.cuda.is_available():
+    if not gpu_available():
         pytest.skip("no GPU visible")
     import voxmap_amd as vx
     from voxmap_amd import presets, scenes
@@ -67,8 +67,7 @@ def test_cli_frame_equals_python_host(built, tmp_path, source):
 def test_cli_ranks_one_frame_equals_python_host(built, tmp_path):
     """vxrender --ranks 1: the forked rank process, the RCCL id through the pipe,
     vx_mgpu_create / vx_mgpu_render (this box has one GPU; N ranks need N GPUs)."""
-    import torch
-    if not torch.cuda.is_available():
+    if not gpu_available():
         pytest.skip("no GPU visible")
     import voxmap_amd as vx
     from voxmap_amd import presets, scenes

@@ -11,6 +11,8 @@ import math
 import numpy as np
 import pytest
 
+from gpu_rig import sun_dir as _sun
+
 NO_DOOM = 0x20000       # include/voxmap.h VX_FLAG_NO_DOOM (oracle/vxo.h VXO_FLAG_NO_DOOM)
 Q, EPS, HCAP = 8, 1.0 / 64.0, 120
 
@@ -76,11 +78,6 @@ def _doom_numpy(field, dirs, max_steps):
     if sx < 0:
         code = code[:, :, ::-1]
     return np.ascontiguousarray(code), (sx, sy, xlo, xhi, ylo, yhi, hmax)
-
-
-def _sun(el_deg, az_deg):
-    el, az = math.radians(el_deg), math.radians(az_deg)
-    return (math.cos(el) * math.cos(az), math.cos(el) * math.sin(az), math.sin(el))
 
 
 # every sign pattern of (r_x, r_y) with r_z > 0, steep to low (slopes up to 4)

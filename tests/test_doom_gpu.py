@@ -8,31 +8,12 @@ agree with vxo_field_doom and march_ex landing by landing in count); at the
 bench scenes (S-proc, S-glass, C5's 3^3 field) with C5's 16 soft samples frames
 are identical with and without the table and the table removes shadow fetches.
 Hard and soft shadows read the table."""
-import math
-
 import numpy as np
 import pytest
 
+from gpu_rig import bin_scene, need_gpu, sun_dir as _sun  # noqa: F401 (need_gpu: an autouse fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-def _gpu():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:  # pragma: no cover
-        return False
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu(built):
-    if not _gpu():
-        pytest.skip("no GPU visible")
-
-
-def _sun(el_deg, az_deg):
-    el, az = math.radians(el_deg), math.radians(az_deg)
-    return (math.cos(el) * math.cos(az), math.cos(el) * math.sin(az), math.sin(el))
 
 
 # soft shadows, and hard shadows (one sample)
@@ -46,8 +27,7 @@ def small(noise):
     from voxmap_amd import scenes
     dims = (96, 64, 40)
     field = vx.field_build(scenes.small_proc(31, dims=dims, n_boxes=30, n_glass=5))
-    sc = vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                  noise_format=vx.FORMAT_BIN, dims=dims, device=0)
+    sc = bin_scene(field, noise, dims)
     yield sc, field
     sc.close()
 

@@ -4,26 +4,12 @@ picks; frames are bit-identical with the tables, with the orthant copies only
 and with none, over suns that need new cone copies (the scene keeps two, so
 the third evicts one) and frames in flight on two streams right after a sun
 change; the work counters equal the oracle's with the same tables."""
-import math
-
 import numpy as np
 import pytest
 
+from gpu_rig import assert_counters_equal, assert_words_equal, bin_scene, need_gpu, sun_dir as _sun  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-def _gpu():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:  # pragma: no cover
-        return False
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu(built):
-    if not _gpu():
-        pytest.skip("no GPU visible")
 
 
 @pytest.fixture(scope="module")
@@ -32,15 +18,9 @@ def scene(noise):
     from voxmap_amd import scenes
     dims = (128, 64, 24)
     field = vx.field_build(scenes.small_proc(31, dims=dims, n_boxes=20, n_glass=5))
-    sc = vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                  noise_format=vx.FORMAT_BIN, dims=dims, device=0)
+    sc = bin_scene(field, noise, dims)
     yield sc, field
     sc.close()
-
-
-def _sun(el_deg, az_deg):
-    el, az = math.radians(el_deg), math.radians(az_deg)
-    return (math.cos(el) * math.cos(az), math.cos(el) * math.sin(az), math.sin(el))
 
 
 # (elevation, azimuth): windows (kx, ky) = (2, 1), (1, 2), (1, 1), (2, 3) in
@@ -222,8 +202,7 @@ def test_c3_full_size_no_exit_equals_exit_tables(noise, flags):
     import voxmap_amd as vx
     from voxmap_amd import presets
     field = vx.field_build(presets.scene_grid("s_proc"))
-    with vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                  noise_format=vx.FORMAT_BIN, dims=(1024, 256, 32), device=0) as sc:
+    with bin_scene(field, noise, (1024, 256, 32)) as sc:
         fr = presets.camera_frame("K1", 3840, 2160, flags=flags)
         a, sa = sc.render(fr, stats=True)
         fn = presets.camera_frame("K1", 3840, 2160, flags=flags | vx.FLAG_NO_EXIT)
@@ -262,11 +241,8 @@ def _literal_subset(sc, fr, W, H, O, every=16):
     a, b = img[rows], ref[rows]
     assert not np.isnan(a).any() and not np.isnan(b).any()
     assert acc["pixels"] == len(rows) * W and acc["shadow_fetches"] > 0
-    bad = int(np.count_nonzero(a.view(np.uint32) != b.view(np.uint32)))
-    assert bad == 0, f"{bad} words differ from the literal march"
-    g = st.as_dict()
-    for k, v in acc.items():
-        assert g[k] == v, (k, g[k], v)
+    assert_words_equal(a, b)                # the literal march's
+    assert_counters_equal(st, acc)
     return rows, a
 
 
@@ -319,8 +295,7 @@ def test_c3_reflect_all_full_size_literal_march(noise):
     f = vx.FLAG_FULL_QUALITY | vx.FLAG_REFLECT_ALL
     fd = presets.camera_frame("K1", 3840, 2160, flags=f)
     fl = presets.camera_frame("K1", 3840, 2160, flags=f | vx.FLAG_NO_EXIT)
-    with vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                  noise_format=vx.FORMAT_BIN, dims=(1024, 256, 32), device=0) as sc:
+    with bin_scene(field, noise, (1024, 256, 32)) as sc:
         sa, _ = _frames_equal_and_literal(sc, fd, fl, 3840, 2160, oracle.Oracle(field, noise, exit=False))
     assert sa.reflect_rays > 6_000_000
 
@@ -338,7 +313,6 @@ def test_s_glass_c3_full_size_literal_march(noise, order):
     f = vx.FLAG_FULL_QUALITY | order
     fd = presets.camera_frame("K1", 3840, 2160, flags=f)
     fl = presets.camera_frame("K1", 3840, 2160, flags=f | vx.FLAG_NO_EXIT)
-    with vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                  noise_format=vx.FORMAT_BIN, dims=(1024, 256, 32), device=0) as sc:
+    with bin_scene(field, noise, (1024, 256, 32)) as sc:
         sa, _ = _frames_equal_and_literal(sc, fd, fl, 3840, 2160, oracle.Oracle(field, noise, exit=False))
     assert sa.glass_px > 100000

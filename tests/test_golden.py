@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from gpu_rig import assert_counters_equal, bin_scene, gpu_available
+
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 META = json.load(open(os.path.join(HERE, "frames.json")))
 
@@ -79,15 +81,13 @@ def test_oracle_exit_tables_keep_golden(built, case):
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", META, ids=[c["name"] for c in META])
 def test_hip_reproduces_golden(built, case):
-    import torch
-    if not torch.cuda.is_available():
+    if not gpu_available():
         pytest.skip("no GPU")
     import voxmap_amd as vx
     mg = _load()
     field, noise, fr, w, h = mg.inputs(case)
     Z, Y, X, _ = field.shape
-    with vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                  noise_format=vx.FORMAT_BIN, dims=(X, Y, Z), device=0) as sc:
+    with bin_scene(field, noise, (X, Y, Z)) as sc:
         dev = sc.read_field()
         assert np.array_equal(dev[..., :3], field[..., :3])
         img, st = sc.render(fr, stats=True)                  # with the sun exit tables
@@ -98,8 +98,7 @@ def test_hip_reproduces_golden(built, case):
     for k, v in case["stats"].items():
         assert getattr(st_lit, k) == v, k
     _, ost = _exit_oracle(case.get("scene") or case["name"], field, noise).render(fr.params, w, h)
-    for k, v in ost.as_dict().items():
-        assert getattr(st, k) == v, k
+    assert_counters_equal(st, ost)
 
 
 def test_blend_stage_decides_bright_panes(built):

@@ -6,24 +6,14 @@ the sun's cone copies recycled after a stream that read them was destroyed (the
 scene keeps no stream handle of the caller's: cone_copy).  Every frame is
 compared with the same pixels rendered by vx_render alone."""
 import ctypes as C
-import math
 import os
 
 import numpy as np
 import pytest
 
+from gpu_rig import bin_scene, need_gpu, sun_dir as _sun  # noqa: F401 (need_gpu: an autouse fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu(built):
-    try:
-        import torch
-        ok = torch.cuda.is_available()
-    except Exception:  # pragma: no cover
-        ok = False
-    if not ok:
-        pytest.skip("no GPU visible")
 
 
 @pytest.fixture(scope="module")
@@ -32,8 +22,7 @@ def scene(noise):
     from voxmap_amd import scenes
     dims = (192, 96, 24)
     field = vx.field_build(scenes.small_proc(41, dims=dims, n_boxes=24, n_glass=6))
-    sc = vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                  noise_format=vx.FORMAT_BIN, dims=dims, device=0)
+    sc = bin_scene(field, noise, dims)
     yield sc
     sc.close()
 
@@ -153,11 +142,6 @@ def test_tile_lists_from_two_threads(scene):
     for t in ts:
         t.join()
     assert not errors, errors[:5]
-
-
-def _sun(el_deg, az_deg):
-    el, az = math.radians(el_deg), math.radians(az_deg)
-    return (math.cos(el) * math.cos(az), math.cos(el) * math.sin(az), math.sin(el))
 
 
 def test_cone_recycle_after_reader_stream_destroyed(scene):

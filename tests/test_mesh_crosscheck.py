@@ -14,6 +14,8 @@ import math
 import numpy as np
 import pytest
 
+from gpu_rig import bin_scene, gpu_available
+
 CASES = [
     # seed, dims, sbj, rot, n_glass
     (5, (64, 32, 16), (32.0, 16.0, 18.0), (1.1, 0.0, 0.6), 4),                 # oblique, K1-like
@@ -124,15 +126,13 @@ def test_oracle_primary_matches_greedy_mesh(built, case):
 def test_hip_primary_only_matches_greedy_mesh(built, case):
     """libvoxmap_hip.so in PRIMARY_ONLY mode (palette colour of the first
     surface, BASELINE C1) against the nearest front face of the mesh."""
-    import torch
-    if not torch.cuda.is_available():
+    if not gpu_available():
         pytest.skip("no GPU visible")
     import voxmap_amd as vx
     grid, field, noise, fr, _, dirs, quads, M = _setup(case)
     Z, Y, X = grid.shape
     fr.params.flags = vx.FLAG_PRIMARY_ONLY
-    with vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                  noise_format=vx.FORMAT_BIN, dims=(X, Y, Z), device=0) as sc:
+    with bin_scene(field, noise, (X, Y, Z)) as sc:
         img, _ = sc.render(fr)
     img = img.reshape(-1, 4)
     from oracle import vxo_palette

@@ -11,17 +11,15 @@ import sys
 
 import pytest
 
+from gpu_rig import gpu_available
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_two_ranks_on_one_gpu_gather_the_frame(built):
-    try:
-        import torch
-        if not torch.cuda.is_available():
-            pytest.skip("no GPU visible")
-    except Exception:  # pragma: no cover
-        pytest.skip("no torch")
+    if not gpu_available():
+        pytest.skip("no GPU visible")
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)

@@ -13,52 +13,10 @@ import math
 import numpy as np
 import pytest
 
+from gpu_rig import (assert_bytes_equal, assert_counters_equal, assert_no_cap_hits, assert_words_equal, bin_scene,
+                     need_gpu, quantise_rgba8, vis_colour)  # noqa: F401 (need_gpu: an autouse fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-def _torch_gpu():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:  # pragma: no cover
-        return False
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu(built):
-    if not _torch_gpu():
-        pytest.skip("no GPU visible")
-
-
-def _scene(vx, field, noise, dims):
-    X, Y, Z = dims
-    return vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                    noise_format=vx.FORMAT_BIN, dims=(X, Y, Z), device=0)
-
-
-def _vis(b):
-    """The traversal's colour: meshed palette indices 1..21 (sdf.cpp:284), else 0 (include/voxmap.h)."""
-    return np.where((b >= 1) & (b <= 21), b, 0).astype(np.uint8)
-
-
-def _diff(a, b):
-    return int(np.count_nonzero(a.view(np.uint32) != b.view(np.uint32)))
-
-
-def _counters_equal(st, ost, keys=None):
-    g, o = st.as_dict(), ost.as_dict()
-    for k in keys or o:
-        assert g[k] == o[k], (k, g[k], o[k])
-
-
-def _compare(img, ref, rows=None):
-    if rows is not None:
-        img, ref = img[rows], ref[rows]
-    bad = _diff(img, ref)
-    if bad:
-        idx = np.argwhere(img.view(np.uint32) != ref.view(np.uint32))[:5]
-        rel = np.max(np.abs(img - ref) / np.maximum(np.abs(ref), 1e-6))
-        raise AssertionError(f"{bad} words differ (max rel {rel:.3g}); first at {idx.tolist()}")
 
 
 SMALL = [
@@ -78,15 +36,13 @@ def test_small_frames_bit_exact(seed, dims, sbj, rot, noise):
     grid = scenes.small_proc(seed, dims=dims, n_boxes=16, n_glass=6)
     field = vx.field_build(grid)
     fr = vx.make_frame(sbj, rot, 160, 96)
-    with _scene(vx, field, noise, dims) as sc:
+    with bin_scene(field, noise, dims) as sc:
         dev_field = sc.read_field()
         img, st = sc.render(fr, stats=True)
     ref, ost = oracle.Oracle(dev_field, noise, exit=True).render(fr.params, 160, 96)
-    _compare(img, ref)
-    g, o = st.as_dict(), ost.as_dict()
-    for k in o:
-        assert g[k] == o[k], (k, g[k], o[k])
-    assert st.primary_cap_hits == 0
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
+    assert_no_cap_hits(st)
 
 
 @pytest.mark.parametrize("octant", range(8))
@@ -96,12 +52,12 @@ def test_field_octant_copies_match_oracle(noise, octant):
     from voxmap_amd import scenes
     dims = (160, 72, 20)
     field = vx.field_build(scenes.small_proc(17, dims=dims, n_boxes=24, n_glass=4))
-    with _scene(vx, field, noise, dims) as sc:
+    with bin_scene(field, noise, dims) as sc:
         dev = sc.read_field(octant)
         box = sc.read_boxes(octant)
     assert np.array_equal(dev[..., :3], field[..., :3])
     assert np.array_equal(dev[..., 3], oracle.field_octant(field, octant))
-    assert np.array_equal(box[..., 0], _vis(field[..., 2]))
+    assert np.array_equal(box[..., 0], vis_colour(field[..., 2]))
     assert np.array_equal(box[..., 1:], oracle.field_box(field, octant))
 
 
@@ -120,7 +76,7 @@ def test_box_extents_full_scene_match_oracle(octant):
         box = sc.read_boxes(octant)
     r = oracle.field_octant(field, octant)
     e = oracle.field_box(field, octant, r_cube=r)
-    assert np.array_equal(box[..., 0], _vis(field[..., 2]))
+    assert np.array_equal(box[..., 0], vis_colour(field[..., 2]))
     assert np.array_equal(box[..., 1:], e)
     assert np.array_equal(e.min(axis=3), r)
 
@@ -130,7 +86,7 @@ def full_scene(noise):
     import voxmap_amd as vx
     from voxmap_amd import presets
     field = vx.field_build(presets.scene_grid("s_proc"))
-    sc = _scene(vx, field, noise, (1024, 256, 32))
+    sc = bin_scene(field, noise, (1024, 256, 32))
     yield sc, sc.read_field()
     sc.close()
 
@@ -146,9 +102,9 @@ def test_baseline_sizes_full_frame(full_scene, noise, cfg, cam):
     fr = presets.camera_frame(cam, c["w"], c["h"])
     img, st = sc.render(fr, stats=True)
     ref, ost = oracle.Oracle(dev_field, noise, exit=True).render(fr.params, c["w"], c["h"], threads=16)
-    _compare(img, ref)
-    _counters_equal(st, ost)
-    assert st.primary_cap_hits == 0
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
+    assert_no_cap_hits(st)
     assert st.pixels == c["w"] * c["h"]
 
 
@@ -162,8 +118,7 @@ def test_rgba8_is_quantised_rgba32f(full_scene, w, h):
     fr = presets.camera_frame("K1", w, h, flags=vx.FLAG_FULL_QUALITY)
     f32, _ = sc.render(fr)
     u8, _ = sc.render(fr, pixel_format=vx.PIXEL_RGBA8)
-    expect = (np.clip(f32, 0, 1) * np.float32(255) + np.float32(0.5)).astype(np.uint8)
-    assert np.array_equal(u8, expect)
+    assert_bytes_equal(u8, quantise_rgba8(f32))
 
 
 @pytest.mark.parametrize("cam", ["K0", "K1", "K2"])
@@ -232,11 +187,11 @@ def test_edge_params(noise, case):
     elif case == "sun_tiny_component":
         kw["sun"] = (0.8, 1e-4, 0.6)         # below the fast path's 2^-10 bound: literal march
     fr = vx.make_frame((48.0, 24.0, 18.0), (1.1, 0.0, 0.6), 128, 80, **kw)
-    with _scene(vx, field, noise, dims) as sc:
+    with bin_scene(field, noise, dims) as sc:
         dev_field = sc.read_field()
         img, st = sc.render(fr, stats=True)
     ref, ost = oracle.Oracle(dev_field, noise, exit=True).render(fr.params, 128, 80)
-    _compare(img, ref)
+    assert_words_equal(img, ref)
     assert st.shadow_fetches == ost.shadow_fetches
 
 
@@ -246,11 +201,11 @@ def test_campus_scene(noise):
     from voxmap_amd import presets, scenes
     field = vx.field_build(scenes.s_campus())
     fr = presets.camera_frame("K1", 480, 270)
-    with _scene(vx, field, noise, (1024, 256, 32)) as sc:
+    with bin_scene(field, noise, (1024, 256, 32)) as sc:
         dev_field = sc.read_field()
         img, _ = sc.render(fr)
     ref, _ = oracle.Oracle(dev_field, noise, exit=True).render(fr.params, 480, 270, threads=16)
-    _compare(img, ref)
+    assert_words_equal(img, ref)
 
 
 # ---- extensions: REFLECT, ROUGH, soft shadows -------------------
@@ -284,15 +239,13 @@ def test_extensions_bit_exact(seed, dims, sbj, rot, noise, case):
     grid = scenes.small_proc(seed, dims=dims, n_boxes=16, n_glass=10)
     field = vx.field_build(grid)
     fr = vx.make_frame(sbj, rot, 160, 96, **EXT_CASES[case])
-    with _scene(vx, field, noise, dims) as sc:
+    with bin_scene(field, noise, dims) as sc:
         dev_field = sc.read_field()
         img, st = sc.render(fr, stats=True)
     ref, ost = oracle.Oracle(dev_field, noise, exit=True).render(fr.params, 160, 96)
-    _compare(img, ref)
-    g, o = st.as_dict(), ost.as_dict()
-    for k in o:
-        assert g[k] == o[k], (k, g[k], o[k])
-    assert st.primary_cap_hits == 0
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
+    assert_no_cap_hits(st)
 
 
 @pytest.mark.parametrize("case", ["soft8", "soft8_pool", "soft6_pool", "soft16_brick", "soft12_full_brick"])
@@ -308,12 +261,12 @@ def test_soft_shadow_paths_at_ragged_sizes(noise, case, w, h):
     seed, dims, sbj, rot = SMALL[0]
     field = vx.field_build(scenes.small_proc(seed, dims=dims, n_boxes=16, n_glass=10))
     fr = vx.make_frame(sbj, rot, w, h, **EXT_CASES[case])
-    with _scene(vx, field, noise, dims) as sc:
+    with bin_scene(field, noise, dims) as sc:
         dev_field = sc.read_field()
         img, st = sc.render(fr, stats=True)
     ref, ost = oracle.Oracle(dev_field, noise, exit=True).render(fr.params, w, h)
-    _compare(img, ref)
-    _counters_equal(st, ost)
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
 
 
 @pytest.mark.parametrize("cfg,cam,kw", [
@@ -332,14 +285,13 @@ def test_extensions_baseline_full_frame(full_scene, noise, cfg, cam, kw):
     fr = presets.camera_frame(cam, c["w"], c["h"], **kw)
     img, st = sc.render(fr, stats=True)
     ref, ost = oracle.Oracle(dev_field, noise, exit=True).render(fr.params, c["w"], c["h"], threads=16)
-    _compare(img, ref)
-    _counters_equal(st, ost)
-    assert st.primary_cap_hits == 0
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
+    assert_no_cap_hits(st)
     assert st.reflect_rays == st.glass_px
     if cfg == "C3":
         img8, _ = sc.render(fr, pixel_format=vx.PIXEL_RGBA8)
-        q = (np.clip(ref, 0, 1) * np.float32(255) + np.float32(0.5)).astype(np.uint8)
-        assert np.array_equal(img8, q)
+        assert_bytes_equal(img8, quantise_rgba8(ref))
 
 
 # ---- f-1: the distance field built on the GPU ----------------------------------
@@ -369,7 +321,7 @@ def test_scene_from_grid_equals_scene_from_field(noise):
     dims = (96, 48, 16)
     grid = scenes.small_proc(12, dims=dims, n_boxes=14, n_glass=5)
     field = vx.field_build(grid)
-    with _scene(vx, field, noise, dims) as a, vx.Scene(map_bytes=grid.tobytes(), map_format=vx.FORMAT_GRID,
+    with bin_scene(field, noise, dims) as a, vx.Scene(map_bytes=grid.tobytes(), map_format=vx.FORMAT_GRID,
                                                      noise_bytes=noise.tobytes(), noise_format=vx.FORMAT_BIN,
                                                      dims=dims, device=0) as b:
         for o in (0, 3, 7):
@@ -416,9 +368,9 @@ def test_c5_full_frame_soft_shadows_full_quality(noise):
     assert np.array_equal(own, oct_e[main])          # the device's boxes of that octant, at the C5 size
     oct_e[main] = own
     ref, ost = oracle.Oracle(field, noise, oct_e=oct_e, exit=True).render(fr.params, c["w"], c["h"], threads=16)
-    _compare(img, ref)
-    _counters_equal(st, ost)
-    assert st.primary_cap_hits == 0
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
+    assert_no_cap_hits(st)
 
 
 def test_soft_pool_equals_per_sample_march(noise):
@@ -472,7 +424,7 @@ def test_air_b22_and_b0_render_identically(noise, tmp_path):
     fr = vx.make_frame((64.0, 32.0, 14.0), (1.2, 0.0, 2.0), 160, 96, flags=vx.FLAG_FULL_QUALITY)
     imgs, sts = [], []
     for f in (f22, f0):
-        with _scene(vx, f, noise, dims) as sc:
+        with bin_scene(f, noise, dims) as sc:
             img, st = sc.render(fr, stats=True)
             assert np.array_equal(sc.read_field()[..., :3], f[..., :3])     # B read back as uploaded
         imgs.append(img)
@@ -480,7 +432,7 @@ def test_air_b22_and_b0_render_identically(noise, tmp_path):
     assert np.array_equal(imgs[0].view(np.uint32), imgs[1].view(np.uint32))
     assert sts[0] == sts[1] and sts[0]["glass_px"] > 100
     ref, _ = oracle.Oracle(f22, noise, exit=True).render(fr.params, 160, 96)
-    _compare(imgs[0], ref)
+    assert_words_equal(imgs[0], ref)
 
 
 def test_hand_edited_map_with_large_radii_uses_the_checked_march(noise):
@@ -496,10 +448,10 @@ def test_hand_edited_map_with_large_radii_uses_the_checked_march(noise):
     field[..., 0][air] = np.minimum(255, field[..., 0][air].astype(int) * 9).astype(np.uint8)   # R up to 144+
     field[5, 10, 10, 0] = 200
     fr = vx.make_frame((48.0, 24.0, 18.0), (1.1, 0.0, 0.6), 128, 80)
-    with _scene(vx, field, noise, dims) as sc:
+    with bin_scene(field, noise, dims) as sc:
         img, st = sc.render(fr, stats=True)
     ref, ost = oracle.Oracle(field, noise, exit=True).render(fr.params, 128, 80)
-    _compare(img, ref)
+    assert_words_equal(img, ref)
     assert st.shadow_fetches == ost.shadow_fetches
 
 
@@ -570,12 +522,11 @@ def test_c1_primary_only_every_pixel(noise):
     c = presets.CONFIGS["C1"]
     field = vx.field_build(presets.scene_grid("s_proc"))
     fr = presets.camera_frame(c["camera"], c["w"], c["h"], flags=vx.FLAG_PRIMARY_ONLY)
-    with _scene(vx, field, noise, (1024, 256, 32)) as sc:
+    with bin_scene(field, noise, (1024, 256, 32)) as sc:
         img, st = sc.render(fr, stats=True)
     ref, ost = oracle.Oracle(field, noise, exit=True).render(fr.params, c["w"], c["h"])
-    _compare(img, ref)
-    for k in ("pixels", "sky_px", "block_px", "glass_px", "primary_fetches"):
-        assert getattr(st, k) == getattr(ost, k), k
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost, keys=("pixels", "sky_px", "block_px", "glass_px", "primary_fetches"))
     assert st.shadow_rays == 0 and st.ao_samples == 0
 
 
@@ -600,7 +551,7 @@ def test_c4_full_frame_as_eight_rank_band_lists(full_scene, noise):
     img = frame.cpu().numpy()
     del frame
     ref, _ = oracle.Oracle(dev_field, noise, exit=True).render(fr.params, w, h, threads=16)
-    _compare(img, ref)
+    assert_words_equal(img, ref)
     del img, ref
     whole = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda:0")
     sc.render_device(fr, whole.data_ptr(), pixel_format=vx.PIXEL_RGBA8)
@@ -630,13 +581,12 @@ def test_2d_mode_bit_exact(noise, case):
                     "grazing": ((-10.0, 32.0, 6.0), (1.5, 0.0, -math.pi / 2))}[case]
         fr = vx.make_frame(sbj, rot, 160, 96, quality=0)
     field = vx.field_build(grid)
-    with _scene(vx, field, noise, dims) as sc:
+    with bin_scene(field, noise, dims) as sc:
         img, st = sc.render(fr, stats=True)
         assert sc.vertex2d() == vx.vertex2d(field)          # the scene's 2D mesh = the host restatement
     ref, ost = oracle.Oracle(field, noise, exit=True).render(fr.params, fr.width, fr.height)
-    _compare(img, ref)
-    for k in ("pixels", "sky_px", "block_px", "glass_px", "primary_fetches"):
-        assert getattr(st, k) == getattr(ost, k), k
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost, keys=("pixels", "sky_px", "block_px", "glass_px", "primary_fetches"))
     if case == "glass_scene":
         assert st.glass_px > 50 and st.block_px > 1000
     if case == "camera_below":

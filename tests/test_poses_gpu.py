@@ -16,11 +16,12 @@ import numpy as np
 import pytest
 
 import test_poses
+from gpu_rig import Rig, gpu_available
 from test_poses import EVEN, MODES_2D, NAMES, ODD, P22, THRESHOLDS, TIMES, frame_from_basis, frame_of, poses, sizes_of
 
 pytestmark = pytest.mark.gpu
 
-INT_INDEX, UNIT_GBUF, GLASS_ORDER, REFLECT_ALL, PRIMARY_ONLY = 0x40, 0x800, 0x1000, 0x2000, 0x8
+UNIT_GBUF, GLASS_ORDER, REFLECT_ALL, PRIMARY_ONLY = 0x800, 0x1000, 0x2000, 0x8
 MODES = {
     "v1": dict(flags=0),
     "full": dict(flags=0x30),
@@ -32,70 +33,13 @@ MODES = {
 }
 
 
-def _torch_gpu():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:  # pragma: no cover
-        return False
-
-
-class Rig:
-    """The field on the device, the copy it reads back, and the oracle over that copy."""
-
-    def __init__(self, noise):
-        import oracle
-        import voxmap_amd as vx
-        field = test_poses.field()
-        self.scene = vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                              noise_format=vx.FORMAT_BIN, dims=test_poses.DIMS, device=0)
-        self.dev_field = self.scene.read_field()
-        self.oracle = oracle.Oracle(self.dev_field, noise, exit=True)
-
-    def check(self, fr, int_index=True, rgba8=False):
-        """One frame against the oracle: NaN exactly where the oracle has NaN (payload and sign are not
-        compared: x86's 0/0 and the GPU's differ), every other word bit-equal, every counter the oracle keeps,
-        no cap hit; then with VX_FLAG_INT_INDEX the same words and counters."""
-        import voxmap_amd as vx
-        w, h = fr.width, fr.height
-        img, st = self.scene.render(fr, stats=True)
-        ref, ost = self.oracle.render(fr.params, w, h)
-        _same(img, ref)
-        g, o = st.as_dict(), ost.as_dict()
-        for k in o:
-            assert g[k] == o[k], (k, g[k], o[k])
-        assert st.primary_cap_hits == 0
-        if int_index:
-            assert not fr.params.flags & INT_INDEX
-            p2 = fr.params.copy()
-            p2.flags |= INT_INDEX
-            img2, st2 = self.scene.render(vx.Frame(p2, w, h), stats=True)
-            _same(img2, img)
-            g2 = st2.as_dict()
-            for k in g:
-                assert k == "kernel_ms" or g2[k] == g[k], (k, g2[k], g[k])
-        if rgba8:
-            assert not np.isnan(ref).any()
-            img8, _ = self.scene.render(fr, pixel_format=vx.PIXEL_RGBA8)
-            assert np.array_equal(img8, (np.clip(ref, 0, 1) * np.float32(255) + np.float32(0.5)).astype(np.uint8))
-        return ref, g
-
-
-def _same(img, ref):
-    nan = np.isnan(ref)
-    assert np.array_equal(np.isnan(img), nan), "NaN at other positions"
-    a, b = img.view(np.uint32)[~nan], ref.view(np.uint32)[~nan]
-    bad = int(np.count_nonzero(a != b))
-    assert bad == 0, f"{bad} words differ; first at {np.argwhere((img.view(np.uint32) != ref.view(np.uint32)) & ~nan)[:5].tolist()}"
-
-
 @pytest.fixture(scope="module")
 def rig(built, noise):
-    if not _torch_gpu():
+    if not gpu_available():
         pytest.skip("no GPU visible")
-    r = Rig(noise)
+    r = Rig(test_poses.field(), noise, test_poses.DIMS)
     yield r
-    r.scene.close()
+    r.close()
     test_poses._state.clear()
 
 

@@ -7,37 +7,9 @@ stacked-glass scene S-glass and a non-default mesh CHUNK."""
 import numpy as np
 import pytest
 
+from gpu_rig import assert_counters_equal, assert_words_equal, bin_scene, need_gpu  # noqa: F401 (need_gpu: autouse)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu(built):
-    try:
-        import torch
-        ok = torch.cuda.is_available()
-    except Exception:  # pragma: no cover
-        ok = False
-    if not ok:
-        pytest.skip("no GPU visible")
-
-
-def _scene(vx, field, noise, dims, **kw):
-    X, Y, Z = dims
-    return vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                    noise_format=vx.FORMAT_BIN, dims=(X, Y, Z), device=0, **kw)
-
-
-def _compare(img, ref):
-    bad = int(np.count_nonzero(img.view(np.uint32) != ref.view(np.uint32)))
-    if bad:
-        idx = np.argwhere(img.view(np.uint32) != ref.view(np.uint32))[:5]
-        raise AssertionError(f"{bad} words differ; first at {idx.tolist()}")
-
-
-def _counters_equal(st, ost):
-    g, o = st.as_dict(), ost.as_dict()
-    for k in o:
-        assert g[k] == o[k], (k, g[k], o[k])
 
 
 @pytest.mark.parametrize("seed,dims,chunk", [(0, (64, 32, 16), 0), (1, (70, 40, 16), 0), (2, (96, 48, 24), 8),
@@ -47,7 +19,7 @@ def test_face_table_matches_oracle_small(noise, seed, dims, chunk):
     import voxmap_amd as vx
     from voxmap_amd import scenes
     field = vx.field_build(scenes.small_proc(seed, dims=dims, n_boxes=12, n_glass=4))
-    with _scene(vx, field, noise, dims, mesh_chunk=chunk) as sc:
+    with bin_scene(field, noise, dims, mesh_chunk=chunk) as sc:
         q = sc.read_face_quads()
     ref = oracle.face_quads(field, chunk)
     assert (ref != 0xFFFF).sum() > 1000
@@ -88,11 +60,11 @@ def test_small_frames_both_splits(noise, seed, dims, sbj, rot, flags, samples, q
     field = vx.field_build(scenes.small_proc(seed, dims=dims, n_boxes=16, n_glass=6))
     f = flags | (0 if quad else vx.FLAG_UNIT_GBUF)
     fr = vx.make_frame(sbj, rot, 160, 96, flags=f, shadow_samples=samples, sun_radius=0.04)
-    with _scene(vx, field, noise, dims) as sc:
+    with bin_scene(field, noise, dims) as sc:
         img, st = sc.render(fr, stats=True)
     ref, ost = oracle.Oracle(field, noise, exit=True, quad=quad).render(fr.params, 160, 96)
-    _compare(img, ref)
-    _counters_equal(st, ost)
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
 
 
 @pytest.mark.parametrize("flags", [0, 48], ids=["v1", "full"])
@@ -103,11 +75,11 @@ def test_c3_unit_split_matches_oracle(noise, flags):
     from voxmap_amd import presets
     field = vx.field_build(presets.scene_grid("s_proc"))
     fr = presets.camera_frame("K1", 3840, 2160, flags=flags | vx.FLAG_UNIT_GBUF)
-    with _scene(vx, field, noise, (1024, 256, 32)) as sc:
+    with bin_scene(field, noise, (1024, 256, 32)) as sc:
         img, st = sc.render(fr, stats=True)
     ref, ost = oracle.Oracle(field, noise, exit=True, quad=False).render(fr.params, 3840, 2160, threads=16)
-    _compare(img, ref)
-    _counters_equal(st, ost)
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
 
 
 @pytest.mark.parametrize("cam,flags", [("K0", 48), ("K1", 48), ("K2", 48), ("K1", 0)])
@@ -123,14 +95,14 @@ def test_s_glass_c3_default_draw_order(noise, cam, flags):
     field = vx.field_build(presets.scene_grid("s_glass"))
     fr = presets.camera_frame(cam, 3840, 2160, flags=flags)
     fo = presets.camera_frame(cam, 3840, 2160, flags=flags | vx.FLAG_GLASS_ORDER)
-    with _scene(vx, field, noise, (1024, 256, 32)) as sc:
+    with bin_scene(field, noise, (1024, 256, 32)) as sc:
         img, st = sc.render(fr, stats=True)
         img_o, st_o = sc.render(fo, stats=True)
     ref, ost = oracle.Oracle(field, noise, exit=True).render(fr.params, 3840, 2160, threads=16)
-    _compare(img, ref)
-    _counters_equal(st, ost)
-    _compare(img_o, img)
-    _counters_equal(st_o, ost)
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
+    assert_words_equal(img_o, img)
+    assert_counters_equal(st_o, ost)
     assert st.glass_px > 100000
 
 
@@ -145,11 +117,11 @@ def test_s_glass_c3_single_layer(noise, cam):
     grid = presets.scene_grid("s_glass")
     field = vx.field_build(grid)
     fr = presets.camera_frame(cam, 3840, 2160, flags=vx.FLAG_FULL_QUALITY | vx.FLAG_GLASS_SINGLE)
-    with _scene(vx, field, noise, (1024, 256, 32)) as sc:
+    with bin_scene(field, noise, (1024, 256, 32)) as sc:
         img, st = sc.render(fr, stats=True)
     ref, ost = oracle.Oracle(field, noise, exit=True).render(fr.params, 3840, 2160, threads=16)
-    _compare(img, ref)
-    _counters_equal(st, ost)
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
     assert st.glass_px > 100000
 
 
@@ -162,15 +134,15 @@ def test_mesh_chunk_option(noise):
     dims = (128, 64, 32)
     field = vx.field_build(scenes.small_proc(21, dims=dims, n_boxes=20, n_glass=6))
     fr = vx.make_frame((64.0, 32.0, 30.0), (1.1, 0.0, 0.6), 200, 120, flags=48)
-    with _scene(vx, field, noise, dims, mesh_chunk=16) as sc:
+    with bin_scene(field, noise, dims, mesh_chunk=16) as sc:
         q = sc.read_face_quads()
         img, st = sc.render(fr, stats=True)
     ref_q = oracle.face_quads(field, 16)
     assert np.array_equal(q, ref_q)
     assert not np.array_equal(ref_q, oracle.face_quads(field, 0))
     ref, ost = oracle.Oracle(field, noise, exit=True, quad=ref_q, chunk=16).render(fr.params, 200, 120)
-    _compare(img, ref)
-    _counters_equal(st, ost)
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
 
 
 GLASS_CASES = [
@@ -198,12 +170,12 @@ def test_glass_order_small(noise, seed, dims, sbj, rot, flags, samples):
     from voxmap_amd import scenes
     field = vx.field_build(scenes.s_glass(seed, dims=dims, n_houses=12, n_facades=4))
     fr = vx.make_frame(sbj, rot, 200, 120, flags=flags, shadow_samples=samples, sun_radius=0.04)
-    with _scene(vx, field, noise, dims) as sc:
+    with bin_scene(field, noise, dims) as sc:
         img, st = sc.render(fr, stats=True)
     O = oracle.Oracle(field, noise, exit=True)
     ref, ost = O.render(fr.params, 200, 120)
-    _compare(img, ref)
-    _counters_equal(st, ost)
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
     assert st.glass_px > 500
 
 
@@ -216,11 +188,11 @@ def test_s_glass_c3_draw_order(noise, cam):
     from voxmap_amd import presets
     field = vx.field_build(presets.scene_grid("s_glass"))
     fr = presets.camera_frame(cam, 3840, 2160, flags=vx.FLAG_FULL_QUALITY | vx.FLAG_GLASS_ORDER)
-    with _scene(vx, field, noise, (1024, 256, 32)) as sc:
+    with bin_scene(field, noise, (1024, 256, 32)) as sc:
         img, st = sc.render(fr, stats=True)
     ref, ost = oracle.Oracle(field, noise, exit=True).render(fr.params, 3840, 2160, threads=16)
-    _compare(img, ref)
-    _counters_equal(st, ost)
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
 
 
 @pytest.mark.parametrize("seed,dims,sbj,rot", SMALL)
@@ -232,11 +204,11 @@ def test_reflect_all_small(noise, seed, dims, sbj, rot, flags):
     from voxmap_amd import scenes
     field = vx.field_build(scenes.small_proc(seed, dims=dims, n_boxes=16, n_glass=6))
     fr = vx.make_frame(sbj, rot, 160, 96, flags=flags)
-    with _scene(vx, field, noise, dims) as sc:
+    with bin_scene(field, noise, dims) as sc:
         img, st = sc.render(fr, stats=True)
     ref, ost = oracle.Oracle(field, noise, exit=True).render(fr.params, 160, 96)
-    _compare(img, ref)
-    _counters_equal(st, ost)
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
     assert st.reflect_rays >= st.block_px
 
 
@@ -247,11 +219,11 @@ def test_reflect_all_c3(noise):
     from voxmap_amd import presets
     field = vx.field_build(presets.scene_grid("s_proc"))
     fr = presets.camera_frame("K1", 3840, 2160, flags=vx.FLAG_FULL_QUALITY | vx.FLAG_REFLECT_ALL)
-    with _scene(vx, field, noise, (1024, 256, 32)) as sc:
+    with bin_scene(field, noise, (1024, 256, 32)) as sc:
         img, st = sc.render(fr, stats=True)
     ref, ost = oracle.Oracle(field, noise, exit=True).render(fr.params, 3840, 2160, threads=16)
-    _compare(img, ref)
-    _counters_equal(st, ost)
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
     assert st.reflect_rays > 6_000_000
 
 
@@ -265,11 +237,11 @@ def test_glass_more_than_eight_panes(noise):
     O = oracle.Oracle(field, noise, exit=True)
     for flags in (48, 48 | 0x1000):
         fr = vx.make_frame((45.0 - 5.4, 12.2, 5.4), (1.5707, 0.0, np.pi / 2), 64, 64, flags=flags)
-        with _scene(vx, field, noise, (64, 24, 12)) as sc:
+        with bin_scene(field, noise, (64, 24, 12)) as sc:
             img, st = sc.render(fr, stats=True)
         ref, ost = O.render(fr.params, 64, 64)
-        _compare(img, ref)
-        _counters_equal(st, ost)
+        assert_words_equal(img, ref)
+        assert_counters_equal(st, ost)
         assert (O.glass_layers(fr.params, 64, 64) >= 9).sum() > 400
 
 
@@ -284,7 +256,7 @@ def test_scene_without_face_table(noise, monkeypatch):
     dims = (96, 64, 16)
     field = vx.field_build(scenes.s_glass(2, dims=dims, n_houses=12, n_facades=4))
     monkeypatch.setenv("VOXMAP_TEST_NO_FACE_TABLE", "1")
-    sc = _scene(vx, field, noise, dims)
+    sc = bin_scene(field, noise, dims)
     monkeypatch.delenv("VOXMAP_TEST_NO_FACE_TABLE")
     with sc:
         for flags in (48, 48 | vx.FLAG_UNIT_GBUF, 48 | vx.FLAG_GLASS_SINGLE,
@@ -298,6 +270,6 @@ def test_scene_without_face_table(noise, monkeypatch):
                            flags=48 | vx.FLAG_UNIT_GBUF | vx.FLAG_GLASS_SINGLE)
         img, st = sc.render(fr, stats=True)
     ref, ost = oracle.Oracle(field, noise, exit=True, quad=False).render(fr.params, 200, 120)
-    _compare(img, ref)
-    _counters_equal(st, ost)
+    assert_words_equal(img, ref)
+    assert_counters_equal(st, ost)
     assert st.glass_px > 500

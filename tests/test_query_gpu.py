@@ -11,24 +11,12 @@ import math
 import numpy as np
 import pytest
 
+from gpu_rig import Rig, need_gpu  # noqa: F401 (need_gpu: an autouse fixture)
+
 pytestmark = pytest.mark.gpu
 
 GLASS = 21
 INF = np.float32(np.inf)
-
-
-def _torch_gpu():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:  # pragma: no cover
-        return False
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu(built):
-    if not _torch_gpu():
-        pytest.skip("no GPU visible")
 
 
 # ---- scenes: the smallest the project uses for parity -------------------------
@@ -58,25 +46,24 @@ CAMS["odd"] = CAMS["odd_cap3"] = [((18.5, 14.5, 11.2), (1.0, 0.0, 0.6)), ((-5.0,
 ODD_SCENES = ["odd", "odd_cap3"]
 
 
-class World:
+class World(Rig):
     """One scene on the device, its oracle, and the reference walk."""
 
     def __init__(self, name):
-        import oracle
         import voxmap_amd as vx
         self.vx = vx
         self.name = name
         self.grid = _grid(name)
         Z, Y, X = self.grid.shape
         self.dims = (X, Y, Z)
-        field = vx.field_build(self.grid)
-        noise = np.zeros((4, 4, 4), np.uint8)
-        self.scene = vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                              noise_format=vx.FORMAT_BIN, noise_size=(4, 4), dims=self.dims, device=0,
-                              dist_cap=DIST_CAP.get(name, 0))
-        self.oracle = oracle.Oracle(self.scene.read_field(), noise, cap=DIST_CAP.get(name, 64))
+        super().__init__(vx.field_build(self.grid), np.zeros((4, 4, 4), np.uint8), self.dims,
+                         dist_cap=DIST_CAP.get(name, 0))
         self._params = vx.make_frame((X / 2, Y / 2, 10.0), (1.0, 0.0, 0.0), 64, 64).params
         self._cache = {}
+
+    def make_oracle(self, noise):
+        import oracle
+        return oracle.Oracle(self.dev_field, noise, cap=DIST_CAP.get(self.name, 64))
 
     def reference(self, rays, key=None):
         """(HIT_DTYPE array, fetches per ray) of the oracle, t_max applied as t < t_max.
@@ -134,7 +121,7 @@ def world(request):
 def _close_worlds():
     yield
     for w in _worlds.values():
-        w.scene.close()
+        w.close()
     _worlds.clear()
 
 

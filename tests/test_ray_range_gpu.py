@@ -16,7 +16,7 @@ away from the origin.  Here a sky-heavy pose is rendered at 64 x 48
     basis' size (the bit clear, the lengths themselves ordinary)
 
 and every frame must equal the oracle's in every fp32 word and counter
-(test_poses_gpu.Rig.check, which also renders through the integer index).  The
+(gpu_rig.Rig.check, which also renders through the integer index).  The
 same frames through vx_render_tiles and vx_render_bands must equal the whole
 frame.  A second pose with blocks and sky takes the same four bases.
 """
@@ -24,8 +24,8 @@ import numpy as np
 import pytest
 
 import test_poses
+from gpu_rig import Rig, gpu_available
 from test_poses import frame_from_basis, poses
-from test_poses_gpu import Rig, _torch_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -36,11 +36,11 @@ BASES = ["unit", "tiny", "huge", "sheared"]
 
 @pytest.fixture(scope="module")
 def rig(built, noise):
-    if not _torch_gpu():
+    if not gpu_available():
         pytest.skip("no GPU visible")
-    r = Rig(noise)
+    r = Rig(test_poses.field(), noise, test_poses.DIMS)
     yield r
-    r.scene.close()
+    r.close()
     test_poses._state.clear()
 
 

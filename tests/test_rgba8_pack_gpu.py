@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import test_poses
+from gpu_rig import bin_scene, gpu_available, quantise_rgba8
 from test_poses import NAMES, frame_of
 
 pytestmark = pytest.mark.gpu
@@ -25,18 +26,7 @@ MODES = {"v1": dict(flags=0), "full": dict(flags=0x30), "reflect_all": dict(flag
 
 def pack(img):
     """floor(clamp(v, 0, 1) * 255 + 0.5) in fp32, one rounding per operation; NaN packs to 0."""
-    v = np.where(np.isnan(img), np.float32(0), img).astype(np.float32)
-    q = np.clip(v, np.float32(0), np.float32(1)) * np.float32(255) + np.float32(0.5)
-    assert q.dtype == np.float32
-    return np.floor(q).astype(np.uint8)
-
-
-def _gpu():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:  # pragma: no cover
-        return False
+    return quantise_rgba8(np.where(np.isnan(img), np.float32(0), img).astype(np.float32))
 
 
 def both(scene, fr):
@@ -48,11 +38,9 @@ def both(scene, fr):
 
 @pytest.fixture(scope="module")
 def scene(built, noise):
-    if not _gpu():
+    if not gpu_available():
         pytest.skip("no GPU visible")
-    import voxmap_amd as vx
-    sc = vx.Scene(map_bytes=test_poses.field().tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                  noise_format=vx.FORMAT_BIN, dims=test_poses.DIMS, device=0)
+    sc = bin_scene(test_poses.field(), noise, test_poses.DIMS)
     yield sc
     sc.close()
     test_poses._state.clear()
@@ -71,15 +59,14 @@ def test_rgba8_is_the_packed_float_frame(mode, scene):
 
 def test_glass_wall_over_bright_sky(built, noise):
     """The blend stage's source: panes over clouds brighter than 1, grazing mirrors (full quality)."""
-    if not _gpu():
+    if not gpu_available():
         pytest.skip("no GPU visible")
     import voxmap_amd as vx
     from voxmap_amd import scenes
     g = scenes.glass_wall()
     Z, Y, X = g.shape
     field = vx.field_build(g)
-    with vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                  noise_format=vx.FORMAT_BIN, dims=(X, Y, Z), device=0) as sc:
+    with bin_scene(field, noise, (X, Y, Z)) as sc:
         for flags in (0x30, 0):
             fr = vx.make_frame((24.0, 20.0, 6.0), (2.1, 0.0, -0.5235987755982988), WH[0], WH[1], flags=flags)
             (f32, st), (u8, _) = sc.render(fr, stats=True), sc.render(fr, pixel_format=vx.PIXEL_RGBA8)

@@ -9,10 +9,10 @@ inputs (its three march modes give one frame), the host builders to the oracle,
 and the scenes to floors on what a frame sees, so that tests/test_shapes_gpu.py
 (which imports the tables and helpers below) compares the kernels with a sound
 reference on frames that are not empty."""
-import math
-
 import numpy as np
 import pytest
+
+from gpu_rig import sun_dir
 
 SEED = 1
 W, H = 100, 70                      # ragged in both directions (not multiples of the 8 x 8 pixel block)
@@ -36,11 +36,6 @@ NOISE_SIZES = [(16, 64), (64, 16), (2, 8), (1, 1)]          # (H, W)
 
 # (elevation, azimuth) with r_z > 0 in the four (r_x, r_y) sign quadrants: ++, -+, --, +-
 QUADRANT_SUNS = [(33, 30), (40, 120), (25, 250), (20, 300)]
-
-
-def sun_dir(el_deg, az_deg):
-    el, az = math.radians(el_deg), math.radians(az_deg)
-    return (math.cos(el) * math.cos(az), math.cos(el) * math.sin(az), math.sin(el))
 
 
 def ids(dims):

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import test_shapes
+from gpu_rig import Rig, assert_counters_equal, assert_words_equal, bin_scene, gpu_available, vis_colour
 from test_shapes import (BASE, CAPS, DIMS, H, LIMIT, NOISE_SIZES, QUADRANT_SUNS, W, camera, field_of, grid_of, ids,
                          random_noise, scene_floors, sun_dir)
 
@@ -25,35 +26,22 @@ pytestmark = pytest.mark.gpu
 FOUR = [BASE, (97, 53, 31)]         # rendered with suns in all four quadrants
 
 
-def _torch_gpu():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:  # pragma: no cover
-        return False
-
-
-def _vis(b):
-    """The traversal's colour: meshed palette indices 1..21, else 0 (include/voxmap.h)."""
-    return np.where((b >= 1) & (b <= 21), b, 0).astype(np.uint8)
-
-
-class Case:
+class Case(Rig):
     """One scene on the device (dims, cap, noise), the copy it reads back as the
     oracle's field, and the oracle in each march mode over one set of boxes."""
 
+    same = staticmethod(assert_words_equal)
+
     def __init__(self, dims, tex, cap=0, **kw):
-        import voxmap_amd as vx
         self.dims, self.cap, self.tex = dims, cap, tex
         self.field = field_of(dims)
-        if tex is not None:
-            kw.update(noise_bytes=tex.tobytes(), noise_format=vx.FORMAT_BIN, noise_size=(tex.shape[1], tex.shape[0]))
-        self.scene = vx.Scene(map_bytes=self.field.tobytes(), map_format=vx.FORMAT_BIN, dims=dims, device=0,
-                              dist_cap=cap, **kw)
-        self.dev_field = self.scene.read_field()
         self._oracles = {}
+        super().__init__(self.field, tex, dims, dist_cap=cap, **kw)
 
-    def oracle(self, mode=True):
+    def make_oracle(self, noise):
+        return None                                     # check() names its own: oracle_in(mode)
+
+    def oracle_in(self, mode=True):
         import oracle
         if mode not in self._oracles:
             first = next(iter(self._oracles.values()), None)
@@ -63,20 +51,9 @@ class Case:
 
     def check(self, fr, mode=True, rgba8=True):
         """One frame against the oracle in `mode`: every fp32 word, every counter
-        the oracle keeps, no cap hit, and the RGBA8 frame == the oracle's quantised."""
-        import voxmap_amd as vx
-        img, st = self.scene.render(fr, stats=True)
-        ref, ost = self.oracle(mode).render(fr.params, W, H)
-        bad = int(np.count_nonzero(img.view(np.uint32) != ref.view(np.uint32)))
-        assert bad == 0, f"{bad} words differ; first at {np.argwhere(img.view(np.uint32) != ref.view(np.uint32))[:5].tolist()}"
-        g, o = st.as_dict(), ost.as_dict()
-        for k in o:
-            assert g[k] == o[k], (k, g[k], o[k])
-        assert st.primary_cap_hits == 0
-        if rgba8:
-            img8, _ = self.scene.render(fr, pixel_format=vx.PIXEL_RGBA8)
-            assert np.array_equal(img8, (np.clip(ref, 0, 1) * np.float32(255) + np.float32(0.5)).astype(np.uint8))
-        return img, g
+        the oracle keeps, no cap hit, and the RGBA8 frame == the oracle's quantised.
+        Returns the frame (the oracle's, which is the device's word for word)."""
+        return super().check(fr, int_index=False, rgba8=rgba8, oracle=self.oracle_in(mode))
 
 
 _cases = {}
@@ -84,11 +61,11 @@ _cases = {}
 
 @pytest.fixture(scope="module", autouse=True)
 def _scenes(built):
-    if not _torch_gpu():
+    if not gpu_available():
         pytest.skip("no GPU visible")
     yield
     for c in _cases.values():
-        c.scene.close()
+        c.close()
     _cases.clear()
     test_shapes._fields.clear()
 
@@ -108,7 +85,7 @@ def _copies_equal_the_oracle(sc, field, cap):
         assert np.array_equal(dev[..., :3], field[..., :3]), o
         r = oracle.field_octant(field, o, cap)
         assert np.array_equal(dev[..., 3], r), o
-        assert np.array_equal(box[..., 0], _vis(field[..., 2])), o
+        assert np.array_equal(box[..., 0], vis_colour(field[..., 2])), o
         assert np.array_equal(box[..., 1:], oracle.field_box(field, o, cap, r_cube=r)), o
 
 
@@ -125,14 +102,12 @@ def test_octant_and_box_copies(dims, noise):
 def test_face_quads(dims, chunk, noise):
     """CHUNK = Z and CHUNK = 5, which divides none of the dims."""
     import oracle
-    import voxmap_amd as vx
     field = field_of(dims)
     want = oracle.face_quads(field, chunk)
     if chunk == 0:
         got = case_of(dims, noise).scene.read_face_quads()
     else:
-        with vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                      noise_format=vx.FORMAT_BIN, dims=dims, device=0, mesh_chunk=chunk) as sc:
+        with bin_scene(field, noise, dims, mesh_chunk=chunk) as sc:
             got = sc.read_face_quads()
     assert np.array_equal(got, want), int(np.count_nonzero(got != want))
     if dims[2] >= 2:
@@ -229,14 +204,13 @@ def test_frames_equal_the_oracle(dims, mode, noise):
         fr = camera(dims, sun=sun_dir(el, az), **kw)
         img, g = c.check(fr)
         if mode == "full" and (el, az) == QUADRANT_SUNS[0]:
-            scene_floors(dims, c.oracle().render(fr.params, W, H)[1])
+            scene_floors(dims, c.oracle_in().render(fr.params, W, H)[1])
         if mode in ("soft16_pool", "soft16_brick"):
             kw["flags"] = 0x30
             base, gb = c.check(camera(dims, sun=sun_dir(el, az), **kw), rgba8=False)
             assert np.array_equal(img.view(np.uint32), base.view(np.uint32)), (el, az)
             if mode == "soft16_pool":
-                for k, _ in oracle.OStats._fields_:
-                    assert g[k] == gb[k], (k, g[k], gb[k])
+                assert_counters_equal(g, gb, keys=[k for k, _ in oracle.OStats._fields_])
             else:
                 kw["flags"] = 0x30 | vx.FLAG_NO_DOOM
                 _, gn = c.check(camera(dims, sun=sun_dir(el, az), **kw), rgba8=False)
@@ -328,9 +302,9 @@ def test_box_cap_at_the_limit(noise):
         _copies_equal_the_oracle(c.scene, c.field, cap)
         assert int(oracle.field_box(c.field, 0, cap)[..., 0].max()) == cap - 1
         c.check(camera(dims))
-        scene_floors(dims, c.oracle().render(camera(dims, flags=0x30).params, W, H)[1])
+        scene_floors(dims, c.oracle_in().render(camera(dims, flags=0x30).params, W, H)[1])
     finally:
-        c.scene.close()
+        c.close()
 
 
 # ---- noise sizes ------------------------------------------------------------------
@@ -361,4 +335,4 @@ def test_synthetic_noise_of_a_given_size():
         assert g["noise_px"] > 0 and g["rough_px"] > 0
         c.check(camera(BASE, sun=sun_dir(*QUADRANT_SUNS[2])), rgba8=False)
     finally:
-        c.scene.close()
+        c.close()

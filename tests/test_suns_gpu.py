@@ -7,17 +7,15 @@ fall on both sides of it and in several octants; slopes of exactly 4 (kx = 5, th
 last column the kernels are sized for) and one ulp over; window bounds on integers; step budgets with no doom
 table and with the last int8 code; zero components on every axis and sign; suns with no tangent frame (every
 soft sample NaN); suns that are not unit length, below the horizon, zero.  Every frame is compared with the
-oracle on every fp32 word and every counter the oracle keeps (test_poses_gpu.Rig.check), then rendered again
+oracle on every fp32 word and every counter the oracle keeps (gpu_rig.Rig.check), then rendered again
 with VX_FLAG_INT_INDEX.  The cases run in test_suns.ORDER, in which consecutive frames need different cone
 windows: the scene keeps two copies, so slots recycle all the time."""
-import copy
-
 import numpy as np
 import pytest
 
 import test_suns
+from gpu_rig import Rig, assert_words_equal_nan_positions, gpu_available, with_flags
 from test_poses import frame_from_basis
-from test_poses_gpu import Rig, _same, _torch_gpu
 from test_suns import (BUDGETS, CASES, FULL, GENERIC, NO_DOOM, ORDER, POSE, SLOPE4, SMALL_DIMS, SMALL_SUNS, SOFT,
                        budget_frame, expected_exit, frame_of, small_frame)
 
@@ -31,34 +29,18 @@ class SunRig(Rig):
     """Rig over any field: the scene, the field it reads back, the oracle with every table over that copy
     (Rig.check compares with it), and the orthant-only and literal oracles over the same boxes."""
 
-    def __init__(self, field, dims, noise):
-        import voxmap_amd as vx
-        self.scene = vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                              noise_format=vx.FORMAT_BIN, dims=dims, device=0)
-        self.dev_field = self.scene.read_field()
-        self.oracle, self.orthant, self.literal = test_suns.make_oracles(self.dev_field, noise)
-
-    def against(self, oracle):
-        """This rig with another of its oracles as the one Rig.check compares with."""
-        r = copy.copy(self)
-        r.oracle = oracle
-        return r
-
-
-def with_flags(fr, flags):
-    import voxmap_amd as vx
-    p = fr.params.copy()
-    p.flags |= flags
-    return vx.Frame(p, fr.width, fr.height)
+    def make_oracle(self, noise):
+        full, self.orthant, self.literal = test_suns.make_oracles(self.dev_field, noise)
+        return full
 
 
 @pytest.fixture(scope="module")
 def rig(built, noise):
-    if not _torch_gpu():
+    if not gpu_available():
         pytest.skip("no GPU visible")
-    r = SunRig(test_suns.field(), test_suns.DIMS, noise)
+    r = SunRig(test_suns.field(), noise, test_suns.DIMS)
     yield r
-    r.scene.close()
+    r.close()
     test_suns._state.clear()
 
 
@@ -76,7 +58,7 @@ def test_sun_frames_equal_the_oracle(name, mode, rig):
     if name in SOFT:
         for extra in (SOFT_POOL, SOFT_POOL | SOFT_BRICK):
             ref2, g2 = rig.check(with_flags(fr, extra))
-            _same(ref2, ref)
+            assert_words_equal_nan_positions(ref2, ref)
             assert g2["shadow_rays"] == g["shadow_rays"]
 
 
@@ -94,9 +76,9 @@ def test_table_modes(name, rig):
         assert (st.shadow_fetches, st.shadow_rays) == (ost.shadow_fetches, ost.shadow_rays), hex(flag)
         if base is None:
             base = img
-            _same(img, ref)
+            assert_words_equal_nan_positions(img, ref)
         else:
-            _same(img, base)
+            assert_words_equal_nan_positions(img, base)
 
 
 @pytest.mark.parametrize("name", ORDER)
@@ -129,7 +111,7 @@ def test_step_budgets(budget, sun, rig):
     fr = budget_frame(sun, budget)
     ref, g = rig.check(fr)
     ref2, g2 = rig.check(with_flags(fr, NO_DOOM))
-    _same(ref2, ref)
+    assert_words_equal_nan_positions(ref2, ref)
     assert g["shadow_rays"] == g2["shadow_rays"] == 2740 and g["shadow_fetches"] <= g2["shadow_fetches"]
     if budget <= 5:
         assert g["shadow_fetches"] == g2["shadow_fetches"]          # no table either way
@@ -142,10 +124,10 @@ def test_small_fields(key, built, noise):
     """37 x 29 x 3 (SB = 5 = kx at slope 4, the limit of launch_sun_cone's guard) and 37 x 29 x 2 (SB < 5: no
     cone); X and Y are no multiples of the doom build's 8-cell block.  Hard and 4-sample soft shadows under the
     default flags, VX_FLAG_NO_DOOM and VX_FLAG_NO_EXIT (that one against the literal oracle)."""
-    if not _torch_gpu():
+    if not gpu_available():
         pytest.skip("no GPU visible")
     dims = SMALL_DIMS[key]
-    r = SunRig(test_suns.small_field(key), dims, noise)
+    r = SunRig(test_suns.small_field(key), noise, dims)
     try:
         for sun in SMALL_SUNS:
             for n, radius in ((0, 0.0), (4, .02)):
@@ -153,15 +135,15 @@ def test_small_fields(key, built, noise):
                 ref, g = r.check(fr)
                 assert g["shadow_rays"] > 0
                 ref2, _ = r.check(with_flags(fr, NO_DOOM))
-                ref3, _ = r.against(r.literal).check(with_flags(fr, NO_EXIT))
-                _same(ref2, ref)
-                _same(ref3, ref)
+                ref3, _ = r.check(with_flags(fr, NO_EXIT), oracle=r.literal)
+                assert_words_equal_nan_positions(ref2, ref)
+                assert_words_equal_nan_positions(ref3, ref)
         info = r.scene.prepare_sun(small_frame(SLOPE4))
         got = (info["kind"], info["octant"], info["kx"], info["ky"])
         assert got == ((2, 7, 5, 5) if dims[2] == 3 else (1, 7, -1, -1))
         assert got == expected_exit(small_frame(SLOPE4).params, dims[2])
     finally:
-        r.scene.close()
+        r.close()
         test_suns._state.pop(key, None)
 
 

@@ -5,21 +5,9 @@ shapes coincide; compact bands.  Every pixel equals the whole frame's."""
 import numpy as np
 import pytest
 
+from gpu_rig import bin_scene, need_gpu  # noqa: F401 (need_gpu: an autouse fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-def _gpu():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:  # pragma: no cover
-        return False
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu(built):
-    if not _gpu():
-        pytest.skip("no GPU visible")
 
 
 @pytest.fixture(scope="module")
@@ -27,8 +15,7 @@ def scene(noise):
     import voxmap_amd as vx
     from voxmap_amd import presets
     field = vx.field_build(presets.scene_grid("s_proc"))
-    with vx.Scene(map_bytes=field.tobytes(), map_format=vx.FORMAT_BIN, noise_bytes=noise.tobytes(),
-                  noise_format=vx.FORMAT_BIN, dims=(1024, 256, 32), device=0) as sc:
+    with bin_scene(field, noise, (1024, 256, 32)) as sc:
         yield sc
 
 
