@@ -22,7 +22,7 @@ SOURCES = ["vx_render_e56.hip", "vx_render_e2.hip", "vx_render_e1.hip", "vx_rend
 # every header under csrc/: an object is rebuilt when any of them is newer (the
 # render kernel's stage headers, vx_math.h .. vx_pixel.h, are included by vx_render.h)
 HEADERS = ["vx_internal.h", "vx_device.h", "vx_math.h", "vx_loads.h", "vx_march.h", "vx_walk.h", "vx_sample.h",
-           "vx_shade.h", "vx_pixel.h", "vx_render.h"]
+           "vx_shade.h", "vx_pool.h", "vx_pixel.h", "vx_render.h"]
 ARCH = os.environ.get("VOXMAP_ARCH", "gfx950")
 # -fno-slp-vectorize: packed FP32 (v_pk_*) issues at the cost of two scalar ops
 # on gfx950 (profiles/r01_valu_costs.txt), so SLP packing only adds moves.

@@ -51,20 +51,7 @@ __global__ __launch_bounds__(kWG) void k_render_2d(KernelArgs a) {
             reinterpret_cast<uint32_t *>(a.out)[out_index<TILED>(a, tile_k, tx0 + sx, ty0 + sy, ox + sx, oy + sy)] =
                 s_px[sy][sx];
     }
-    if (STATS) {
-        unsigned long long v[ST_COUNT] = {};
-        v[ST_PIXELS] = wave_sum(n_px);
-        v[ST_SKY] = wave_sum(n_sky);
-        v[ST_BLOCK] = wave_sum(n_block);
-        v[ST_GLASS] = wave_sum(n_glass);
-        v[ST_PRIM_FETCH] = wave_sum(cnt.prim_fetch);
-        if (lane == 0) {
-            unsigned long long *row = a.stats + (size_t)((blockIdx.x + blockIdx.y * 7) & 63) * ST_COUNT;
-#pragma unroll
-            for (int i = 0; i < ST_COUNT; i++)
-                if (v[i]) atomicAdd(row + i, v[i]);
-        }
-    }
+    if (STATS) flush_counters(a, cnt, n_px, n_sky, n_block, n_glass);   // (only prim_fetch is counted here)
 }
 
 // Scatter compact tile-major pixels into a frame.
@@ -98,28 +85,27 @@ int launch_render(const KernelArgs &a, int fmt, void *stream) {
     dim3 grid = tiled ? dim3(a.n_tiles * (a.tile_w >> kBXS) * (a.tile_h >> kBYS))
                       : dim3((a.w + kBX - 1) / kBX, (a.h + kBY - 1) / kBY);
     if (a.fc.quality == 0) {          // MODE_2D: the vertex2d mesh (render.js:278, 287)
-#define VX_L2(F, S, T) hipLaunchKernelGGL((k_render_2d<F, S, T>), grid, block, 0, s, a)
-#define VX_L2T(F, S) do { if (tiled) VX_L2(F, S, true); else VX_L2(F, S, false); } while (0)
-        if (fmt == VX_PIXEL_RGBA32F) { if (st) VX_L2T(0, true); else VX_L2T(0, false); }
-        else { if (st) VX_L2T(1, true); else VX_L2T(1, false); }
-#undef VX_L2T
-#undef VX_L2
+        launch_variant(fmt, st, tiled, [&](auto F, auto S, auto T) {
+            hipLaunchKernelGGL((k_render_2d<F(), S(), T()>), grid, block, 0, s, a);
+        });
         if (st) hipLaunchKernelGGL(k_reduce_stats, dim3(1), dim3(64), 0, s, a.stats);
         return (int)hipGetLastError();
     }
     const bool brick_ok = a.fc.soft_sg >= 0 && a.sunp && a.fc.soft_lg >= 4 && (a.SXp & 3) == 0 && a.SB >= 9;
     // the general shading block (glass in draw order, REFLECT_ALL): EXT 5 / 6 (not with the pooled pass)
     const bool general = (a.fc.flags & (VX_FLAG_GLASS_ORDER | VX_FLAG_REFLECT_ALL)) != 0;
-    const int ext = a.fc.n_sun > 1 ? (general ? 6 : (a.fc.flags & VX_FLAG_SOFT_BRICK) && brick_ok ? 4
-                                      : (a.fc.flags & (VX_FLAG_SOFT_POOL | VX_FLAG_SOFT_BRICK)) ? 3 : 2)
-                                   : (general ? 5 : (a.fc.flags & (VX_FLAG_REFLECT | VX_FLAG_ROUGH)) ? 1 : 0);
+    const unsigned fl = a.fc.flags;
+    const int ext = a.fc.n_sun > 1 ? (general ? kExtGeneralSoft : (fl & VX_FLAG_SOFT_BRICK) && brick_ok ? kExtSoftBrick
+                                      : (fl & (VX_FLAG_SOFT_POOL | VX_FLAG_SOFT_BRICK)) ? kExtSoftPool : kExtSoft)
+                                   : (general ? kExtGeneralHard : (fl & (VX_FLAG_REFLECT | VX_FLAG_ROUGH)) ? kExtHard
+                                      : kExtV1);
     int rc;
     switch (ext) {
-        case 0: rc = launch_render_e0(a, fmt, grid.x, grid.y, stream); break;
-        case 1: rc = launch_render_e1(a, fmt, grid.x, grid.y, stream); break;
-        case 2: rc = launch_render_e2(a, fmt, grid.x, grid.y, stream); break;
-        case 3: rc = launch_render_e3(a, fmt, grid.x, grid.y, stream); break;
-        case 4: rc = launch_render_e4(a, fmt, grid.x, grid.y, stream); break;
+        case kExtV1: rc = launch_render_e0(a, fmt, grid.x, grid.y, stream); break;
+        case kExtHard: rc = launch_render_e1(a, fmt, grid.x, grid.y, stream); break;
+        case kExtSoft: rc = launch_render_e2(a, fmt, grid.x, grid.y, stream); break;
+        case kExtSoftPool: rc = launch_render_e3(a, fmt, grid.x, grid.y, stream); break;
+        case kExtSoftBrick: rc = launch_render_e4(a, fmt, grid.x, grid.y, stream); break;
         default: rc = launch_render_e56(ext, a, fmt, grid.x, grid.y, stream); break;
     }
     if (rc) return rc;

@@ -243,6 +243,17 @@ int launch_query(const QueryArgs &a, void *stream);
 
 // Launchers (vx_dispatch.hip).  Return a hipError_t as int.
 int launch_render(const KernelArgs &a, int pixel_format, void *stream);
+// The render kernel's modes: k_render's EXT template argument (vx_render.h), an
+// int, so the digit stands in every instantiation's mangled name (ILi<digit>E:
+// kernel_meta.render_params and the recorded profiles read it there).
+// launch_render picks one per frame from n_sun and the frame's flags.
+constexpr int kExtV1 = 0;            // the reference's shader
+constexpr int kExtHard = 1;          // extensions (REFLECT, ROUGH) with the hard shadow
+constexpr int kExtSoft = 2;          // extensions with soft shadows (n_sun samples, marched per lane)
+constexpr int kExtSoftPool = 3;      // kExtSoft, the first surface's samples by the pooled wave pass (VX_FLAG_SOFT_POOL)
+constexpr int kExtSoftBrick = 4;     // kExtSoftPool with LDS brick staging (VX_FLAG_SOFT_BRICK, where the bricks fit)
+constexpr int kExtGeneralHard = 5;   // kExtHard with the general shading block (VX_FLAG_GLASS_ORDER, REFLECT_ALL)
+constexpr int kExtGeneralSoft = 6;   // kExtSoft with it
 // the per-mode launchers launch_render picks from (vx_render_e*.hip: each is
 // launch_render_ext of vx_render.h over that unit's k_render instantiations)
 int launch_render_e0(const KernelArgs &a, int fmt, unsigned gx, unsigned gy, void *stream);

@@ -1,8 +1,10 @@
 // vx_pixel.h — a pixel's way in and out of a render kernel: the block shape,
-// the view ray, packing and stores, the primary-only colour, and the 2D
-// mode's shading (k_render_2d, vx_dispatch.hip).  Shared by k_render
-// (vx_render.h) and the dispatch unit, which does not include k_render.
+// the view ray, packing and stores, the primary-only colour, the counters'
+// flush, the host's (format, stats, tiled) launch ladder, and the 2D mode's
+// shading (k_render_2d, vx_dispatch.hip).  Shared by k_render (vx_render.h)
+// and the dispatch unit, which does not include k_render.
 #pragma once
+#include <type_traits>
 #include "vx_loads.h"
 #include "vx_math.h"
 #include "vx_sample.h"
@@ -72,6 +74,58 @@ __device__ __forceinline__ void primary_only_colour(int n, const Surf &g0, float
     rgba[1] = pc < 22 ? kPalette[pc][1] : 1.0f;
     rgba[2] = pc < 22 ? kPalette[pc][2] : 1.0f;
     rgba[3] = 1.0f;
+}
+
+// The counters' way out of a STATS kernel (k_render, k_render_2d): each wave
+// sums a pixel's counters and the four pixel counts over its lanes, and lane 0
+// adds the sums that are not zero to the block's row of a.stats
+// (k_reduce_stats, vx_dispatch.hip, then sums the rows).
+__device__ __forceinline__ void flush_counters(const KernelArgs &a, const Counters &cnt, unsigned n_px, unsigned n_sky,
+                                               unsigned n_block, unsigned n_glass) {
+    unsigned long long v[ST_COUNT];
+    v[ST_PIXELS] = wave_sum(n_px);
+    v[ST_SKY] = wave_sum(n_sky);
+    v[ST_BLOCK] = wave_sum(n_block);
+    v[ST_GLASS] = wave_sum(n_glass);
+    v[ST_PRIM_FETCH] = wave_sum(cnt.prim_fetch);
+    v[ST_SHADOW_RAYS] = wave_sum(cnt.shadow_rays);
+    v[ST_SHADOW_FETCH] = wave_sum(cnt.shadow_fetch);
+    v[ST_AO] = wave_sum(cnt.ao);
+    v[ST_NOISE_PX] = wave_sum(cnt.noise_px);
+    v[ST_CAP_HITS] = wave_sum(cnt.cap_hit);
+    v[ST_REFL_RAYS] = wave_sum(cnt.refl_rays);
+    v[ST_REFL_FETCH] = wave_sum(cnt.refl_fetch);
+    v[ST_ROUGH] = wave_sum(cnt.rough);
+    v[ST_PRIM_WITERS] = wave_sum(cnt.prim_witers);
+    v[ST_MARCH_WITERS] = wave_sum(cnt.march_witers);
+    v[ST_MARCH_SLOTS] = wave_sum(cnt.march_slots);
+    v[ST_SHADOW_RESOLVED] = wave_sum(cnt.shadow_resolved);
+    if ((threadIdx.x & 63) == 0) {
+        // spread the adds over 64 slot rows to avoid one hot line per counter
+        unsigned long long *row = a.stats + (size_t)((blockIdx.x + blockIdx.y * 7) & 63) * ST_COUNT;
+#pragma unroll
+        for (int i = 0; i < ST_COUNT; i++)
+            if (v[i]) atomicAdd(row + i, v[i]);
+    }
+}
+
+// A launch's (pixel format, stats, tiled) as template arguments: calls
+// f(FMT, STATS, TILED) with three std::integral_constant values (FMT an int,
+// VX_PIXEL_*; the other two bools), so the caller writes its kernel once:
+//   launch_variant(fmt, st, tiled, [&](auto F, auto S, auto T) { ... k<F(), S(), T()> ... });
+template <typename Fn>
+void launch_variant(int fmt, bool stats, bool tiled, Fn f) {
+    const auto pick = [](bool v, auto g) {
+        if (v) g(std::true_type{});
+        else g(std::false_type{});
+    };
+    pick(fmt == VX_PIXEL_RGBA32F, [&](auto f32) {
+        pick(stats, [&](auto S) {
+            pick(tiled, [&](auto T) {
+                f(std::integral_constant<int, f32() ? VX_PIXEL_RGBA32F : VX_PIXEL_RGBA8>{}, S, T);
+            });
+        });
+    });
 }
 
 // ---------------- 2D mode (u_quality = 0) ----------------

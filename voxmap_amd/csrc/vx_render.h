@@ -15,9 +15,11 @@
 //
 // The device code the kernel calls lives in one header per stage, included
 // below in the order the stages run: vx_math.h, vx_loads.h, vx_march.h,
-// vx_walk.h, vx_sample.h, vx_shade.h, vx_pixel.h.  The kernel is tuned to the
-// register; moving text between those headers is free (every kernel's machine
-// code is compared, tools/isa_diff.py), folding it is not.
+// vx_walk.h, vx_sample.h, vx_shade.h, vx_pool.h (the pooled modes' brick
+// march), vx_pixel.h.  The kernel is tuned to the register; moving text
+// between those headers is free (every kernel's machine code is compared,
+// tools/isa_diff.py), folding it is not, nor is a new function boundary
+// (DESIGN.md §3).
 //
 // Numerical contract: fp32, IEEE div/sqrt, no FMA contraction
 // (built with -ffp-contract=off), GLSL built-ins spelled out, vexp2
@@ -48,6 +50,7 @@
 #include "vx_walk.h"
 #include "vx_sample.h"
 #include "vx_shade.h"
+#include "vx_pool.h"
 #include "vx_pixel.h"
 
 namespace vx {
@@ -57,8 +60,9 @@ namespace {
 // EXT: 0 = v1 (the reference's shader), 1 = extensions (REFLECT, ROUGH,
 // REFLECT_ALL) with the hard shadow, 2 = extensions with soft shadows (n sun
 // samples), 3 = 2 with the first surface's samples marched by the pooled wave
-// pass (VX_FLAG_SOFT_POOL), 4 = 3 with LDS brick staging (VX_FLAG_SOFT_BRICK),
-// 5 / 6 = 1 / 2 with glass in draw order (VX_FLAG_GLASS_ORDER).  Each
+// pass (VX_FLAG_SOFT_POOL), 4 = 3 with LDS brick staging (VX_FLAG_SOFT_BRICK,
+// march_brick: vx_pool.h), 5 / 6 = 1 / 2 with glass in draw order
+// (VX_FLAG_GLASS_ORDER); named kExt* in vx_internal.h.  Each
 // instantiation carries only its own code and registers; soft shadows in a
 // kernel of their own also keep the sun_k[0] / sun_k[k] addresses apart (a
 // pointer phi between them makes the compiler copy KernelArgs to scratch).
@@ -374,32 +378,7 @@ if constexpr (!kGeneral) {
         a.blk_time[2 * b + 1] = __builtin_amdgcn_s_memrealtime();
     }
 #endif
-    if (STATS) {
-        unsigned long long v[ST_COUNT];
-        v[ST_PIXELS] = wave_sum(n_px);
-        v[ST_SKY] = wave_sum(n_sky);
-        v[ST_BLOCK] = wave_sum(n_block);
-        v[ST_GLASS] = wave_sum(n_glass);
-        v[ST_PRIM_FETCH] = wave_sum(cnt.prim_fetch);
-        v[ST_SHADOW_RAYS] = wave_sum(cnt.shadow_rays);
-        v[ST_SHADOW_FETCH] = wave_sum(cnt.shadow_fetch);
-        v[ST_AO] = wave_sum(cnt.ao);
-        v[ST_NOISE_PX] = wave_sum(cnt.noise_px);
-        v[ST_CAP_HITS] = wave_sum(cnt.cap_hit);
-        v[ST_REFL_RAYS] = wave_sum(cnt.refl_rays);
-        v[ST_REFL_FETCH] = wave_sum(cnt.refl_fetch);
-        v[ST_ROUGH] = wave_sum(cnt.rough);
-        v[ST_PRIM_WITERS] = wave_sum(cnt.prim_witers);
-        v[ST_MARCH_WITERS] = wave_sum(cnt.march_witers);
-        v[ST_MARCH_SLOTS] = wave_sum(cnt.march_slots);
-        v[ST_SHADOW_RESOLVED] = wave_sum(cnt.shadow_resolved);
-        if (lane == 0) {
-            // spread the adds over 64 slot rows to avoid one hot line per counter
-            unsigned long long *row = a.stats + (size_t)((blockIdx.x + blockIdx.y * 7) & 63) * ST_COUNT;
-#pragma unroll
-            for (int i = 0; i < ST_COUNT; i++) atomicAdd(row + i, v[i]);
-        }
-    }
+    if (STATS) flush_counters(a, cnt, n_px, n_sky, n_block, n_glass);
 }
 
 // One EXT mode's render launches: every (format, stats, tiled, primary index)
@@ -424,13 +403,7 @@ int launch_render_ext(const KernelArgs &a, int fmt, unsigned gx, unsigned gy, vo
     const dim3 grid = t3 ? dim3((unsigned)(a.tile_w >> kBXS), (unsigned)(a.tile_h >> kBYS), (unsigned)a.n_tiles)
                          : dim3(gx, gy);
     const bool st = a.stats != nullptr, tiled = a.tile_ids != nullptr;
-    if (fmt == VX_PIXEL_RGBA32F) {
-        if (st) { if (tiled) launch_k<0, true, true, E>(a, grid, s); else launch_k<0, true, false, E>(a, grid, s); }
-        else { if (tiled) launch_k<0, false, true, E>(a, grid, s); else launch_k<0, false, false, E>(a, grid, s); }
-    } else {
-        if (st) { if (tiled) launch_k<1, true, true, E>(a, grid, s); else launch_k<1, true, false, E>(a, grid, s); }
-        else { if (tiled) launch_k<1, false, true, E>(a, grid, s); else launch_k<1, false, false, E>(a, grid, s); }
-    }
+    launch_variant(fmt, st, tiled, [&](auto F, auto S, auto T) { launch_k<F(), S(), T(), E>(a, grid, s); });
     return (int)hipGetLastError();
 }
 

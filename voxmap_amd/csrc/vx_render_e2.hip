@@ -4,6 +4,6 @@
 
 namespace vx {
 int launch_render_e2(const KernelArgs &a, int fmt, unsigned gx, unsigned gy, void *stream) {
-    return launch_render_ext<2>(a, fmt, gx, gy, stream);
+    return launch_render_ext<kExtSoft>(a, fmt, gx, gy, stream);
 }
 }  // namespace vx

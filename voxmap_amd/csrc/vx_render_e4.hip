@@ -4,6 +4,6 @@
 
 namespace vx {
 int launch_render_e4(const KernelArgs &a, int fmt, unsigned gx, unsigned gy, void *stream) {
-    return launch_render_ext<4>(a, fmt, gx, gy, stream);
+    return launch_render_ext<kExtSoftBrick>(a, fmt, gx, gy, stream);
 }
 }  // namespace vx

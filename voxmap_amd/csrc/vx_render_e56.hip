@@ -9,6 +9,7 @@
 
 namespace vx {
 int launch_render_e56(int ext, const KernelArgs &a, int fmt, unsigned gx, unsigned gy, void *stream) {
-    return ext == 6 ? launch_render_ext<6>(a, fmt, gx, gy, stream) : launch_render_ext<5>(a, fmt, gx, gy, stream);
+    return ext == kExtGeneralSoft ? launch_render_ext<kExtGeneralSoft>(a, fmt, gx, gy, stream)
+                                  : launch_render_ext<kExtGeneralHard>(a, fmt, gx, gy, stream);
 }
 }  // namespace vx

@@ -32,8 +32,8 @@ RENDER_SCRATCH_LIMIT = 256      # bytes per thread: spill slots yes, a KernelArg
 STATS_SCRATCH_LIMIT = 0
 STATS_SPILL_LIMIT = 0
 # VGPR spill slots allowed per EXT mode of a timed (non-STATS) k_render
-# instantiation (0 v1, 1 extensions, 2 soft shadows, 3 pooled, 4 LDS bricks, 5/6
-# general).  The rare paths (glass in draw order where panes stack, the stacked
+# instantiation (the modes 0-6 are listed once, as kExt* in csrc/vx_internal.h).
+# The rare paths (glass in draw order where panes stack, the stacked
 # chain) spill at the 8-wave budget; what must never spill is a
 # hot loop -- hot_loop_spills() checks the march and primary loops themselves.
 # Each limit is the largest count of the current build plus a small margin
