@@ -285,7 +285,7 @@ static void scene_consts(vx_scene *s) {
     std::memset(&a, 0, sizeof a);
     a.prim = s->d_prim.get();
     a.sun = s->d_sun.get(); a.sunp = s->d_sunp.get(); a.sunx = s->d_sunx.get();
-    a.SB = s->SB; a.SBf = (float)s->SB; a.SXp = s->SXp;
+    a.SB = s->SB; a.SBf = (float)s->SB; a.SXp = s->SXp; a.SXpf = (float)s->SXp;
     a.SXpYp = (unsigned)s->SXp * (unsigned)s->SYp;
     a.sunp_texels = (unsigned)s->SXp * (unsigned)s->SYp * (unsigned)s->SZp;
     a.rg = s->d_rg.get(); a.rg2 = s->d_rg2.get();
@@ -294,10 +294,13 @@ static void scene_consts(vx_scene *s) {
     a.qface = s->d_qface.get(); a.qcopy = s->d_qcopy.get();
     a.chunk = s->chunk;
     a.X = s->X; a.Y = s->Y; a.Z = s->Z;
+    a.Xf = (float)s->X; a.Yf = (float)s->Y; a.Zf = (float)s->Z;   // float copies: all exact (dimensions < 2^23)
     a.noise_w = s->noise_w; a.noise_h = s->noise_h;
+    a.noise_wf = (float)s->noise_w; a.noise_hf = (float)s->noise_h;
     a.noise_rw = 1.0f / (float)s->noise_w; a.noise_rh = 1.0f / (float)s->noise_h;   // powers of two: exact
     while ((1 << a.noise_lw) < s->noise_w) a.noise_lw++;
     a.Xp = s->L.Xp; a.pad = s->L.pad;
+    a.Xpf = (float)s->L.Xp; a.Xp4f = (float)(4 * s->L.Xp);
     a.XpYp = (unsigned)s->L.Xp * (unsigned)s->L.Yp;
     a.XY = (unsigned)s->X * (unsigned)s->Y; a.XYZ = a.XY * (unsigned)s->Z;
     a.copy_texels = (unsigned)s->L.texels;
@@ -305,7 +308,7 @@ static void scene_consts(vx_scene *s) {
     std::memset(&q, 0, sizeof q);
     q.prim = a.prim;
     q.X = s->X; q.Y = s->Y; q.Z = s->Z;
-    q.pad = a.pad; q.Xp = a.Xp; q.XpYp = a.XpYp;
+    q.pad = a.pad; q.Xp = a.Xp; q.Xpf = a.Xpf; q.XpYp = a.XpYp;
     q.copy_texels = a.copy_texels;
 }
 

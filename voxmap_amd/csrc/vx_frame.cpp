@@ -126,6 +126,7 @@ void frame_consts(const vx_frame_params &p, int w, int h, int X, int Y, int Z, i
     fc.rcp_w = 1.0f / fc.fw;
     fc.rcp_h = 1.0f / fc.fh;
     fc.sun_up = p.sun_dir[2] > 0.0f ? 1 : 0;
+    fc.sun_down = p.sun_dir[2] < 0.0f ? 1 : 0;   // the comparison of shadeFactor[] below: false for -0 and NaN
     const float lim = 0.0009765625f;   // 2^-10: keeps every t = d/|r| < 1025, every cell index in int range
     fc.march_fast = fc.sun_abs[0] >= lim && fc.sun_abs[1] >= lim && fc.sun_abs[2] >= lim;
     fc.max_steps = max_steps;
@@ -162,20 +163,21 @@ void frame_consts(const vx_frame_params &p, int w, int h, int X, int Y, int Z, i
     fc.n_sun = p.shadow_samples > 1 ? std::min(p.shadow_samples, VX_MAX_SHADOW_SAMPLES) : 1;
     float dirs[VX_MAX_SHADOW_SAMPLES][3];
     sun_samples(p.sun_dir, p.sun_radius, fc.n_sun, dirs);
-    for (int k = 0; k < fc.n_sun; k++) sun_ray(dirs[k], fc.sun_k[k]);
+    for (int k = 0; k < fc.n_sun; k++) {
+        sun_ray(dirs[k], fc.sun_k[k]);
+        const float *sn = fc.sun_k[k].sign;
+        fc.sun_sg[k] = (sn[0] > 0.0f ? 1 : 0) | (sn[1] > 0.0f ? 2 : 0) | (sn[2] > 0.0f ? 4 : 0);
+    }
     // the pooled soft-shadow march (vx_render.h k_render) runs one loop specialised on
     // the axis signs for every sample: only when they all agree
     fc.soft_sg = -1;
     fc.soft_lg = 0;
     while ((1 << fc.soft_lg) < fc.n_sun) fc.soft_lg++;
     if (fc.n_sun > 1) {
-        auto sg = [](const SunRay &r) {
-            return (r.sign[0] > 0.0f ? 1 : 0) | (r.sign[1] > 0.0f ? 2 : 0) | (r.sign[2] > 0.0f ? 4 : 0);
-        };
         bool same = true;
         for (int k = 0; k < fc.n_sun; k++)
-            same = same && fc.sun_k[k].fast && sg(fc.sun_k[k]) == sg(fc.sun_k[0]) && fc.sun_k[k].up == fc.sun_k[0].up;
-        if (same) fc.soft_sg = sg(fc.sun_k[0]);
+            same = same && fc.sun_k[k].fast && fc.sun_sg[k] == fc.sun_sg[0] && fc.sun_k[k].up == fc.sun_k[0].up;
+        if (same) fc.soft_sg = fc.sun_sg[0];
     }
 }
 

@@ -54,6 +54,8 @@ struct FrameConsts {
     float sun_sign[3];                 // sign(u_sunDir) (render.frag:94)
     float sun_abs[3], sun_rcp[3];      // |u_sunDir|, RN(1/|u_sunDir|)
     int sun_up;                        // u_sunDir.z > 0: march reads R, else G (render.frag:89)
+    int sun_down;                      // u_sunDir.z < 0.0f (render.frag:228; false for -0 and NaN): the ROUGH
+                                       // sun factor's test, one comparison here instead of one per wave
     int march_fast;                    // every 2^-10 <= |u_sunDir_i|: fast exact march path
     int max_steps;                     // MAX_STEPS = 2*Z (render.frag:12)
     float scatterCol[3], spaceCol[3], shadeCol[3];   // render.frag:168-170, 220
@@ -69,6 +71,8 @@ struct FrameConsts {
                                        // of them on the fast path and reading one channel; -1 otherwise
     int soft_lg;                       // ext: log2 of the lanes per fragment in the pooled march (2^lg >= n_sun)
     SunRay sun_k[VX_MAX_SHADOW_SAMPLES];   // ext: soft-shadow sample directions
+    int sun_sg[VX_MAX_SHADOW_SAMPLES]; // per sample, its axis-sign pattern (bit i: r_i > 0): which specialised
+                                       // loop its fast-path march takes (the literal march does not read it)
 };
 
 // Parameters of one render launch (passed by value to the kernel).
@@ -79,6 +83,7 @@ struct KernelArgs {
     int SB;                  // border width of sunp (Z + 2: a march step moves <= Z + 1 cells per axis)
     float SBf;               // (float)SB
     int SXp;                 // padded row length of sunp
+    float SXpf;              // (float)SXp
     unsigned SXpYp, sunp_texels;
     const int8_t *sunx;      // 8 orthant-exit copies of sunp's channel, one per ray octant (bit i: r_i > 0), or nullptr
     const int8_t *sunc;      // the frame's cone-exit copy (every sample of the frame reads it), or nullptr
@@ -94,7 +99,11 @@ struct KernelArgs {
     int chunk;               // the mesh's CHUNK (glass draw order, face_key)
     unsigned long long *blk_time;   // diagnostics build (VX_BLOCK_TIMING): per block start, end; else null
     int X, Y, Z;
+    float Xf, Yf, Zf;        // (float)X, (float)Y, (float)Z: exact, like every float copy of an integer here (the
+                             // kernel has no scalar convert: each (float)n of an argument costs every wave a
+                             // quarter-rate vector instruction)
     int noise_w, noise_h;    // powers of two
+    float noise_wf, noise_hf;    // (float)noise_w, (float)noise_h
     float noise_rw, noise_rh;    // 1/noise_w, 1/noise_h (exact)
     int noise_lw;                // log2(noise_w)
     int w, h;                // frame size
@@ -109,6 +118,7 @@ struct KernelArgs {
     vx_frame_params p;
     int max_shadow_steps;
     int Xp;                  // padded row length (FieldLayout)
+    float Xpf, Xp4f;         // (float)Xp, (float)(4 * Xp)
     int pad;                 // border width of the prim copies (FieldLayout::pad)
     unsigned XpYp;           // padded slice size
     unsigned XY, XYZ;        // X*Y, X*Y*Z
@@ -235,6 +245,7 @@ struct QueryArgs {
     unsigned long long *stats;   // QS_COUNT device counters, or nullptr
     int X, Y, Z;
     int pad, Xp;             // FieldLayout::pad, ::Xp
+    float Xpf;               // (float)Xp
     unsigned XpYp, copy_texels;
     int n;
 };

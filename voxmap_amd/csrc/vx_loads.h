@@ -11,7 +11,8 @@
 namespace vx {
 namespace {
 
-__constant__ float kPalette[22][3] = {
+// (row 22: what a colour past the palette shades as, white -- palette() clamps to it)
+__constant__ float kPalette[23][3] = {
     {0.0f, 0.0f, 0.0f},
     {0.0431373f, 0.0627451f, 0.0745098f},
     {0.133333f, 0.490196f, 0.317647f},
@@ -34,6 +35,7 @@ __constant__ float kPalette[22][3] = {
     {0.984314f, 0.886275f, 0.317647f},
     {1.0f, 1.0f, 1.0f},
     {0.505882f, 0.780392f, 0.831373f},
+    {1.0f, 1.0f, 1.0f},
 };
 
 struct Surf {            // one G-buffer record (what render.vert hands render.frag)
@@ -113,6 +115,15 @@ constexpr uint32_t kSentinel = 0xFFFFFFFFu;   // border cells: colour 0xFF, exte
 template <typename T>
 __device__ __forceinline__ T ld_off(const T *base, unsigned byte_off) {
     return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + byte_off);
+}
+
+// The base colour of palette index c (render.frag: c < 22 ? palette[c] : white):
+// the index clamped onto the table's white row 22 instead of a divergent
+// branch around the fetch, at a 32-bit offset from the table's base.
+__device__ __forceinline__ void palette(int c, float &r, float &g, float &b) {
+    const unsigned off = __umul24(min((unsigned)c, 22u), 12u);
+    const float *base = &kPalette[0][0];
+    r = ld_off(base, off); g = ld_off(base, off + 4u); b = ld_off(base, off + 8u);
 }
 
 // Typed buffer loads: the texture data unit converts the texel.

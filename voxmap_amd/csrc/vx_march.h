@@ -165,7 +165,7 @@ __device__ __forceinline__ bool march_pad_from(const KernelArgs &a, const SunRay
     const float r0 = S.r[0], r1 = S.r[1], r2 = S.r[2];
     const int maxs = a.fc.max_steps;
     if (maxs <= 0) return maxs == 0;
-    const float xpf = (float)a.SXp;
+    const float xpf = a.SXpf;
     const unsigned sxpyp = a.SXpYp;
     float tv = 1.0f;                            // texel of the current cell = safe (render.frag:86: 1)
     // one step of :94-128 -> the offset of the texel to load
@@ -228,7 +228,7 @@ __device__ __forceinline__ bool march_pad_from(const KernelArgs &a, const SunRay
 template <int SG, int DOOM = kDoomNone>   // the sun's axis signs (bit i: r_i > 0); DOOM: see march_pad_from
 __device__ __forceinline__ bool march_pad(const KernelArgs &a, const SunRay &S, const int8_t *sun, float c0, float c1,
                                           float c2, float f0, float f1, float f2, Counters &cnt) {
-    const float xpf = (float)a.SXp;
+    const float xpf = a.SXpf;
     constexpr float kBias = 8388608.0f;
     const float exy = __builtin_fmaf(c1 + a.SBf, xpf, (c0 + a.SBf) + kBias);   // exact integers
     const float e2 = (c2 + a.SBf) + kBias;
@@ -244,7 +244,7 @@ template <int SG>
 __device__ __forceinline__ int march_soft(const KernelArgs &a, const int8_t *sun, float c0, float c1, float c2, float f0,
                                           float f1, float f2, Counters &cnt) {
     const FrameConsts &F = a.fc;
-    const float xpf = (float)a.SXp;
+    const float xpf = a.SXpf;
     constexpr float kBias = 8388608.0f;
     const float exy = __builtin_fmaf(c1 + a.SBf, xpf, (c0 + a.SBf) + kBias);
     const float e2 = (c2 + a.SBf) + kBias;
@@ -258,11 +258,6 @@ __device__ __forceinline__ int march_soft(const KernelArgs &a, const int8_t *sun
         lit += march_pad_from<SG, kDoomAfter>(a, S, rsrc, exy, e2, march_len_d(S, d0, d1, d2), f0, f1, f2, cnt) ? 1 : 0;
     }
     return lit;
-}
-
-// the sign pattern of a fast-path sun ray (bit i: r_i > 0)
-__device__ __forceinline__ int sun_sg(const SunRay &S) {
-    return (S.sign[0] > 0.0f ? 1 : 0) | (S.sign[1] > 0.0f ? 2 : 0) | (S.sign[2] > 0.0f ? 4 : 0);
 }
 
 // Literal path for any other sun direction (zero or tiny components: the
@@ -342,17 +337,18 @@ __device__ __forceinline__ bool first_step_exit(const KernelArgs &a, const int8_
 }
 
 // march(cell, fract, S.r) of render.frag:233 -> "lit" (step == MAX_STEPS, :234).
+// sg: S's axis-sign pattern (FrameConsts::sun_sg), read only where S.fast.
 // S by value: the soft-shadow loop indexes sun_k[k] dynamically, and a
 // reference into the kernel argument there made the compiler copy the whole
 // KernelArgs (1.5 KB) to scratch.
 // (the per-sample soft loop runs only where no cone copy serves every sample,
 // so it never reads a doom code; it keeps the same form, which measured faster)
 template <int DOOM = kDoomAfter>
-__device__ __forceinline__ bool march_sun(const KernelArgs &a, const SunRay S, float c0, float c1, float c2, float f0,
+__device__ __forceinline__ bool march_sun(const KernelArgs &a, const SunRay S, int sg, float c0, float c1, float c2, float f0,
                                           float f1, float f2, Counters &cnt) {
     if (S.fast && a.sunp) {
-        // wave-uniform switch on the frame's sun signs: one specialised loop each
-        const int sg = sun_sg(S);
+        // wave-uniform switch on the sun's axis signs (sg = FrameConsts::sun_sg of S, from the host: a
+        // scalar integer, where three float compares of S.sign ran on the vector unit): one specialised loop each
         // the frame's cone copy, else the octant's orthant copy, else the plain channel
         const int8_t *ch = a.sunc ? a.sunc
                          : a.sunx ? a.sunx + (size_t)sg * a.sunp_texels : S.up ? a.sunp : a.sunp + a.sunp_texels;

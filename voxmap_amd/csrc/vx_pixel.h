@@ -70,9 +70,7 @@ __device__ __forceinline__ void view_ray(const FrameConsts &F, int px, int py, f
 
 __device__ __forceinline__ void primary_only_colour(int n, const Surf &g0, float rgba[4]) {
     const int pc = n == 0 ? 0 : g0.color;
-    rgba[0] = pc < 22 ? kPalette[pc][0] : 1.0f;
-    rgba[1] = pc < 22 ? kPalette[pc][1] : 1.0f;
-    rgba[2] = pc < 22 ? kPalette[pc][2] : 1.0f;
+    palette(pc, rgba[0], rgba[1], rgba[2]);
     rgba[3] = 1.0f;
 }
 

@@ -31,7 +31,7 @@ __device__ __forceinline__ bool march_brick(const KernelArgs &a, const SunRay &S
     const int maxs = a.fc.max_steps;
     if (maxs <= 0) return maxs == 0;
     constexpr float kBias = 8388608.0f;
-    const float xpf = (float)a.SXp;
+    const float xpf = a.SXpf;
     const int8_t *sunb = sun - 0x4B000000;
     float e0 = (c0 + a.SBf) + kBias, e1 = c1 + a.SBf, e2 = (c2 + a.SBf) + kBias;
     // brick origin (padded cells, same biases as the cells)

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(kWG) void k_query(const QueryArgs a) {
                 const uint32_t *pp = a.prim + (size_t)oct * a.copy_texels;
                 const float bx = (float)(B0 + a.pad) - hp0 + 8388608.0f, by = (float)(B1 + a.pad) - hp1,
                             bz = (float)(B2 + a.pad) - hp2 + 8388608.0f;
-                const float fXp = (float)a.Xp;
+                const float fXp = a.Xpf;
                 auto fetch = [&]() -> uint32_t {
                     const unsigned xy = __float_as_uint(__builtin_fmaf(h1 + by, fXp, h0 + bx)) - 0x4B000000u;
                     return pp[xy + __umul24(__float_as_uint(h2 + bz), a.XpYp)];

@@ -8,8 +8,9 @@ namespace vx {
 namespace {
 
 // ---------------- sampling ----------------
-__device__ __forceinline__ void lin_axis(float coord, int size, int &i0, int &i1, float &w) {
-    const float u = coord * (float)size - 0.5f;
+// (fsize = (float)size, from the host: KernelArgs::Xf ..)
+__device__ __forceinline__ void lin_axis(float coord, int size, float fsize, int &i0, int &i1, float &w) {
+    const float u = coord * fsize - 0.5f;
     const float fl = floorf(u);
     w = u - fl;
     // AO coordinates are finite and far inside +-2^24 ((cell + fract) of a
@@ -32,12 +33,12 @@ __device__ __forceinline__ float sdf_lin(const KernelArgs &a, float c0, float c1
     const FrameConsts &F = a.fc;
     int y0, y1, z0, z1;
     float wx, wy, wz;
-    const float ux = (c0 + f0) * F.sf[0] * (float)a.X - 0.5f;
+    const float ux = (c0 + f0) * F.sf[0] * a.Xf - 0.5f;
     const float flx = floorf(ux);
     wx = ux - flx;
     const int px = min(max((int)flx, -1), a.X - 1) + 1;     // pair index (AO coordinates are far inside +-2^24)
-    lin_axis((c1 + f1) * F.sf[1], a.Y, y0, y1, wy);
-    lin_axis((c2 + f2) * F.sf[2], a.Z, z0, z1, wz);
+    lin_axis((c1 + f1) * F.sf[1], a.Y, a.Yf, y0, y1, wy);
+    lin_axis((c2 + f2) * F.sf[2], a.Z, a.Zf, z0, z1, wz);
     // one byte offset and two deltas (0 or one row / plane: the clamped corners
     // differ by at most one cell per axis)
     const unsigned row = (unsigned)a.X + 1u;
@@ -69,14 +70,17 @@ __device__ __forceinline__ float sdf_lin(const KernelArgs &a, float c0, float c1
 // form only for the lanes outside that range (NaN included): floor(fl / n)
 // with the IEEE quotient by n = 2^k, which is exactly fl * 2^-k (fl is 0 or
 // |fl| >= 1: no underflow).
-__device__ __forceinline__ int wrap_idx(float fl, int n) {
+__device__ __forceinline__ int wrap_idx(float fl, int n, float fn) {   // fn = (float)n (KernelArgs::noise_wf, _hf)
     int r = (int)fl & (n - 1);
     if (!(fabsf(fl) < 16777216.0f)) {
-        // 1/n from n (exact: a power of two), not from a kernel argument: a
-        // load sunk into this rare block would be tail-merged across the u/v
-        // calls into a pointer phi -- a KernelArgs copy to scratch
-        const float q = floorf(fl * (1.0f / (float)n));
-        r = f2i(fl - q * (float)n) & (n - 1);
+        // 1/n from fn = 2^k, which the caller's hot path holds in a register already:
+        // its exponent mirrored, 2^-k = bits(2^0) * 2 - bits(2^k), one scalar
+        // subtraction (a division of two scalars would run on the vector unit).  Not
+        // from a kernel argument of its own: a load sunk into this rare block would be
+        // tail-merged across the u/v calls into a pointer phi -- a KernelArgs copy to scratch
+        const float rn = __uint_as_float(0x7F000000u - __float_as_uint(fn));
+        const float q = floorf(fl * rn);
+        r = f2i(fl - q * fn) & (n - 1);
     }
     return r;
 }
@@ -87,10 +91,10 @@ __device__ __forceinline__ int wrap_idx(float fl, int n) {
 // REPEAT-wrapped when it was built): the same RN(b / 255) values.
 __device__ __forceinline__ float fbm(const KernelArgs &a, float px, float py) {
     const int W = a.noise_w, H = a.noise_h;
-    const float u = px * (float)W - 0.5f, v = py * (float)H - 0.5f;
+    const float u = px * a.noise_wf - 0.5f, v = py * a.noise_hf - 0.5f;
     const float fu = floorf(u), fv = floorf(v);
     const float wa = u - fu, wb = v - fv;
-    const int x0 = wrap_idx(fu, W), y0 = wrap_idx(fv, H);
+    const int x0 = wrap_idx(fu, W, a.noise_wf), y0 = wrap_idx(fv, H, a.noise_hf);
     const u32x4 rs = buf_rsrc(a.noise4, kRsrcRGBA);
     const f32x4 t = ld_fmt4(rs, (((unsigned)y0 << a.noise_lw) | (unsigned)x0) << 2);
     const float r0 = gmix(t.x, t.y, wa), r1 = gmix(t.z, t.w, wa);
@@ -119,9 +123,11 @@ __device__ __forceinline__ void sky_clear(const FrameConsts &F, float d0, float 
                                           float &r2, float sky[3]) {
     if (RANGED) normalize3_ranged(d0, d1, d2, r0, r1, r2);
     else normalize3(d0, d1, d2, r0, r1, r2);     // skybox modelled at infinity
-    // reflect(rayDir, (-1,0,0)) (render.frag:155); only .z is read
+    // reflect(rayDir, (-1,0,0)) (render.frag:155); only .z is read.  RANGED (r finite): k is
+    // finite, k * 0 a zero, so r2 - k * 0 is r2, or for r2 = +-0 a zero of either sign -- and
+    // gmax(0, z) below returns its +0 for both zeros: r2 itself gives the same rz
     const float k = 2.0f * ((-1.0f * r0 + 0.0f * r1) + 0.0f * r2);
-    const float refl_z = r2 - k * 0.0f;
+    const float refl_z = RANGED ? r2 : r2 - k * 0.0f;
     const float sunCol[3] = {1.4f, 1.0f, 0.5f};
     float sunFactor = gmax(0.0f, F.sun[0] * r0 + F.sun[1] * r1 + F.sun[2] * r2) - 1.0f;
     const float glow = vexp2(8.0f * sunFactor);
@@ -204,10 +210,10 @@ __device__ __forceinline__ void shade_sky(const KernelArgs &a, float d0, float d
 // from that channel's plane of the quad texture (a.noise4 planes 1..3).
 __device__ __forceinline__ void white(const KernelArgs &a, float px, float py, float &w0, float &w1, float &w2) {
     const int W = a.noise_w, H = a.noise_h;
-    const float u = px * (float)W - 0.5f, v = py * (float)H - 0.5f;
+    const float u = px * a.noise_wf - 0.5f, v = py * a.noise_hf - 0.5f;
     const float fu = floorf(u), fv = floorf(v);
     const float wa = u - fu, wb = v - fv;
-    const int x0 = wrap_idx(fu, W), y0 = wrap_idx(fv, H);
+    const int x0 = wrap_idx(fu, W, a.noise_wf), y0 = wrap_idx(fv, H, a.noise_hf);
     const unsigned off = (((unsigned)y0 << a.noise_lw) | (unsigned)x0) << 2, plane = ((unsigned)W * (unsigned)H) << 2;
     const u32x4 rs = buf_rsrc(a.noise4, kRsrcRGBA);
     const f32x4 tr = ld_fmt4(rs, off + plane), tg = ld_fmt4(rs, off + 2u * plane), tb = ld_fmt4(rs, off + 3u * plane);

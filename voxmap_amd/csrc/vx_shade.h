@@ -28,7 +28,7 @@ __device__ __forceinline__ float block_shade_factor(const KernelArgs &a, const S
     float w0, w1, w2, m0, m1, m2;
     white(a, u * kRoughScale, v * kRoughScale, w0, w1, w2);
     normalize3_ranged(n0 + kRoughAmp * w0, n1 + kRoughAmp * w1, n2 + kRoughAmp * w2, m0, m1, m2);
-    return F.sun[2] < 0.0f ? 0.0f : sqrtf(gmax(0.0f, (m0 * F.sun[0] + m1 * F.sun[1]) + m2 * F.sun[2]));
+    return F.sun_down ? 0.0f : sqrtf(gmax(0.0f, (m0 * F.sun[0] + m1 * F.sun[1]) + m2 * F.sun[2]));
 }
 
 // lit_given >= 0 (EXT 2): the soft-shadow samples of this fragment were
@@ -63,8 +63,8 @@ __device__ __forceinline__ void shade_block(const KernelArgs &a, const Surf &g, 
         // |n + 0.1 w| lies in [0.89, 1.11] (unit axis n, |w_i| <= 1): rcp_ranged is exact
         normalize3_ranged(n0 + kRoughAmp * w0, n1 + kRoughAmp * w1, n2 + kRoughAmp * w2, m0, m1, m2);
     }
-    float base0 = 1.0f, base1 = 1.0f, base2 = 1.0f;
-    if (g.color < 22) { base0 = kPalette[g.color][0]; base1 = kPalette[g.color][1]; base2 = kPalette[g.color][2]; }
+    float base0, base1, base2;
+    palette(g.color, base0, base1, base2);
     float amb0 = 1.0f, amb1 = 1.0f, amb2 = 1.0f;
     if (!(F.flags & VX_FLAG_NO_AO)) {                                                  // :223-225
         cnt.ao++;
@@ -85,20 +85,22 @@ __device__ __forceinline__ void shade_block(const KernelArgs &a, const Surf &g, 
         amb1 = gmix(1.0f, F.shadeCol[1], ambFactor);
         amb2 = gmix(1.0f, F.shadeCol[2], ambFactor);
     }
+    // (a default that ROUGH overwrites, on purpose: as an if / else the compiler splits the
+    // march below by `rough` and its step loop spills -- 51 spill instructions in EXT 1's)
     float shadeFactor = F.shadeFactor[ni];                                             // :228-229
     if (rough)
-        shadeFactor = F.sun[2] < 0.0f ? 0.0f : sqrtf(gmax(0.0f, (m0 * F.sun[0] + m1 * F.sun[1]) + m2 * F.sun[2]));
+        shadeFactor = F.sun_down ? 0.0f : sqrtf(gmax(0.0f, (m0 * F.sun[0] + m1 * F.sun[1]) + m2 * F.sun[2]));
     if (shadeFactor > 0.0f && !(F.flags & VX_FLAG_NO_SHADOW)) {                        // :232-235
         // the exit copy every sample reads (sunc, or the octant's orthant copy
         // when they share one sign pattern): a first step into a marked block is lit
-        const int sg0 = sun_sg(F.sun_k[0]);
+        const int sg0 = F.sun_sg[0];
         const int8_t *xch = EXT != 2 || !a.sunp || !F.sun_k[0].fast ? nullptr
                           : a.sunc ? a.sunc
                           : a.sunx && F.soft_sg >= 0 ? a.sunx + (size_t)sg0 * a.sunp_texels : nullptr;
         const bool first_exit = xch && lit_given < 0 && first_step_exit(a, xch, sg0, g);
         if (EXT != 2) {                // the reference's hard shadow: one sun ray
             cnt.shadow_rays++;
-            const bool lit = march_sun(a, F.sun_k[0], g.c0, g.c1, g.c2, g.f0, g.f1, g.f2, cnt);
+            const bool lit = march_sun(a, F.sun_k[0], sg0, g.c0, g.c1, g.c2, g.f0, g.f1, g.f2, cnt);
             shadeFactor = shadeFactor * (lit ? 1.0f : 0.0f);
         } else if (lit_given >= 0) {   // marched by the wave pass (k_render)
             shadeFactor = shadeFactor * ((float)lit_given / (float)F.n_sun);
@@ -117,9 +119,11 @@ __device__ __forceinline__ void shade_block(const KernelArgs &a, const Surf &g, 
             } else {
                 for (int k = 0; k < F.n_sun; k++) {
                     cnt.shadow_rays++;
-                    lit += march_sun(a, F.sun_k[k], g.c0, g.c1, g.c2, g.f0, g.f1, g.f2, cnt) ? 1 : 0;
+                    lit += march_sun(a, F.sun_k[k], F.sun_sg[k], g.c0, g.c1, g.c2, g.f0, g.f1, g.f2, cnt) ? 1 : 0;
                 }
             }
+            // ((float)F.n_sun stays a convert on the vector unit, once per shaded wave: from the host
+            // as a float it measured C5 +1.0 %, DESIGN.md §3 "Round 8" step 7)
             shadeFactor = shadeFactor * ((float)lit / (float)F.n_sun);
         }
     }
@@ -128,13 +132,15 @@ __device__ __forceinline__ void shade_block(const KernelArgs &a, const Surf &g, 
     const float l2 = F.shadeCol[2] + 0.3f * shadeFactor;
     o[0] = base0; o[1] = base1; o[2] = base2; o[3] = 1.0f;
     if (F.quality > 0) {                                                               // :242-244
-        float nc0 = F.normalCol[ni][0], nc1 = F.normalCol[ni][1], nc2 = F.normalCol[ni][2];
+        float nc0, nc1, nc2;
         if (rough) {                                                                   // :211-217 per fragment
             const float an0 = fabsf(m0), an1 = fabsf(m1), an2 = fabsf(m2);
             nc0 = (0.90f * an0 + 0.95f * an1) + 1.0f * an2;
             nc1 = (0.90f * an0 + 0.95f * an1) + 1.0f * an2;
             nc2 = (0.95f * an0 + 1.00f * an1) + 1.0f * an2;
             if (m2 < 0.0f) { nc0 = nc0 * 0.8f; nc1 = nc1 * 0.8f; nc2 = nc2 * 0.8f; }
+        } else {                                                                       // per axis normal: the host's table
+            nc0 = F.normalCol[ni][0]; nc1 = F.normalCol[ni][1]; nc2 = F.normalCol[ni][2];
         }
         o[0] = o[0] * ((nc0 * l0) * amb0);
         o[1] = o[1] * ((nc1 * l1) * amb1);

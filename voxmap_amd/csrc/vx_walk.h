@@ -149,7 +149,7 @@ __device__ __forceinline__ int primary(const KernelArgs &a, int oct, float d0, f
     // 0x4B000000 + the sum) and z by 2^23 + 2^22 (|z| < 2^21: the low 24 bits
     // of the pattern are 2^22 + z); kz takes both constants back, mod 2^32
     const float kx4 = a.kx4 - (float)(4 * ip0) + 8388608.0f, ky = a.ky - (float)ip1;
-    const float fXp4 = (float)(4 * a.Xp);
+    const float fXp4 = a.Xp4f;
     const unsigned XpYp4 = 4u * a.XpYp;
     const unsigned kz = a.kz - XpYp4 * (unsigned)ip2 + (((unsigned)oct * a.copy_texels) << 2) - 0x4B000000u -
                         (XpYp4 << 22);
@@ -331,7 +331,7 @@ __device__ __forceinline__ int walk_reflect(const KernelArgs &a, int B0, int B1,
     // multiply of the biased bits (their low 24 bits are z)
     const float bx = (float)(B0 + a.pad) - hp0 + 8388608.0f, by = (float)(B1 + a.pad) - hp1,
                 bz = (float)(B2 + a.pad) - hp2 + 8388608.0f;
-    const float fXp = (float)a.Xp;
+    const float fXp = a.Xpf;
     auto fetch = [&]() -> uint32_t {
         const unsigned xy = __float_as_uint(__builtin_fmaf(h1 + by, fXp, h0 + bx)) - 0x4B000000u;
         return pp[xy + __umul24(__float_as_uint(h2 + bz), a.XpYp)];

@@ -28,8 +28,12 @@ RENDER_SCRATCH_LIMIT = 256      # bytes per thread: spill slots yes, a KernelArg
 # then summed wrong shadow_fetches and march counters under frames that were right
 # (soft shadows on the literal march; tests/test_shapes_gpu.py).  They are not timed, so
 # they carry no occupancy floor (vx_render.h VX_OCC_WAVES): 110-145 VGPRs, no VGPR spill
-# and no private segment, and the guard keeps it so.
-STATS_SCRATCH_LIMIT = 0
+# and no scratch access, and the guard keeps it so: no scratch instruction in the
+# kernel's code (scratch_ops), and a private segment of at most the 20 bytes that the
+# compiler reserves, and that nothing reads or writes, when a 128-bit SGPR tuple (a
+# buffer descriptor) is spilled to VGPR lanes: the tuple's unused 16-byte slot and the
+# register scavenger's word.
+STATS_SCRATCH_LIMIT = 20
 STATS_SPILL_LIMIT = 0
 # VGPR spill slots allowed per EXT mode of a timed (non-STATS) k_render
 # instantiation (the modes 0-6 are listed once, as kExt* in csrc/vx_internal.h).
@@ -45,7 +49,10 @@ STATS_SPILL_LIMIT = 0
 # loop; measured faster than the spill-free in-loop form on C3, v1 and
 # REFLECT_ALL (profiles/r06_ab_doom10_c3.txt), so a handful is allowed there
 HOT_LOOP_SPILL_LIMITS = {1: 8, 2: 2, 5: 8}
-SPILL_LIMITS = {0: 19, 1: 62, 2: 64, 3: 70, 4: 132, 5: 16, 6: 16}
+# (EXT 4, the opt-in LDS-brick mode: 134 slots in its fp32 integer-index instantiation since the host's
+# float copies of the dimensions joined the arguments, 130 in the RGBA8 ones; no reshape was tried for a
+# mode that is opt-in and measured slower than the default; re-timed, -5.6 %: profiles/uniform_ab.txt)
+SPILL_LIMITS = {0: 19, 1: 62, 2: 64, 3: 70, 4: 136, 5: 16, 6: 16}
 V1_SCRATCH_LIMIT = 72           # EXT 0's private segment (64 B now): the chain's slots, no KernelArgs copy
 RENDER_VGPR_LIMIT = 64          # 8 waves/SIMD
 GENERAL_VGPR_LIMIT = 96         # EXT 5/6: 5 waves/SIMD (their own unit, vx_render_e56.hip)
@@ -191,6 +198,143 @@ def _hot_spills(body: list[tuple[int, str]]) -> tuple[int, int]:
     return loops, n
 
 
+# ---- wave-uniform work on the vector unit (tools/isa_uniform.py prints the listing) ----
+# gfx950 has no scalar float unit: a float convert or compare of kernel arguments
+# runs on the vector unit, once per wave, at a quarter-rate price, for a result
+# that is the same for the whole frame -- the host passes such values instead
+# (KernelArgs::Xf .., FrameConsts::sun_down, ::sun_sg).  Two counts per kernel:
+#   uniform  VALU instructions none of whose source operands is a vector
+#            register (SGPRs, literals and inline constants only).  Not counted:
+#            moves and lane moves (v_mov, v_readlane, v_writelane,
+#            v_readfirstlane, v_accvgpr), v_mbcnt (the lane id), v_nop, and
+#            v_cndmask, whose SGPR-pair condition is a lane mask as a rule;
+#   kernarg  global loads whose address derives from the kernel-argument
+#            pointer (a per-lane index into a table inside KernelArgs).
+# Per EXT mode, the largest counts over the timed (non-STATS) k_render
+# instantiations of the current build: what is left is listed in
+# profiles/uniform_valu_after.txt and explained line by line in DESIGN.md §3
+# "Round 8" (the slab tests of primary()'s general branch, 2 * cloudTime, face_key's
+# division by CHUNK, the tile prologue's divisions, the soft loops' sample count).
+# A change that moves one is a change to look at, and the limit moves with it.
+UNIFORM_VALU_LIMITS: dict[int, tuple[int, int]] = {0: (19, 6), 1: (21, 10), 2: (49, 14), 3: (51, 14), 4: (50, 22),
+                                                   5: (21, 10), 6: (49, 10)}
+_UNIFORM_SKIP = ("v_mov_", "v_readlane", "v_writelane", "v_readfirstlane", "v_accvgpr", "v_mbcnt", "v_nop", "v_cndmask",
+                 "v_swap")
+_VREG = re.compile(r"(?<![\w.])[va](?:\d+|\[\d+:\d+\])")
+_REG = re.compile(r"(?<![\w.])([sv])(?:(\d+)|\[(\d+):(\d+)\])")
+
+
+def _regs(text: str) -> set[tuple[str, int]]:
+    out = set()
+    for kind, one, lo, hi in _REG.findall(text):
+        out.update((kind, i) for i in (range(int(lo), int(hi) + 1) if lo else (int(one),)))
+    return out
+
+
+def asm_kernels(text: str) -> dict[str, list[str]]:
+    """{symbol: [instruction, ...]} of compiler assembly (hipcc -S: ``name:`` labels,
+    ``;`` comments) or of a disassembly (llvm-objdump -d: ``<name>:`` headers,
+    ``//`` comments): mnemonic and operands, comments and directives dropped."""
+    out: dict[str, list[str]] = {}
+    cur = None
+    for line in text.splitlines():
+        m = re.match(r"^(?:[0-9a-f]+ <(\S+)>:|([A-Za-z_][\w$.]*):)\s*(?:;.*)?$", line)
+        if m:
+            cur = out.setdefault(m.group(1) or m.group(2), [])     # (basic-block labels start with a dot)
+            continue
+        ins = re.split(r";|//", line, 1)[0].strip()
+        if cur is not None and ins and re.match(r"[a-z]+_\w+", ins):
+            cur.append(ins)
+    return out
+
+
+def uniform_scan(body: list[str]) -> tuple[list[str], list[str]]:
+    """(uniform VALU instructions, kernarg-derived global loads) of one kernel's
+    instructions, in program order.  The kernel-argument pointer is the base of the
+    kernel's first s_load; what is computed from it (scalar or vector adds, spills
+    to and from lanes) is followed in program order, not along the control flow."""
+    uniform, kload = [], []
+    karg: set = set()                     # registers (and (vgpr, lane) spill slots) holding a kernarg address
+    seeded = False
+    for ins in body:
+        op, _, rest = ins.partition(" ")
+        ops = [o.strip() for o in re.split(r",(?![^\[]*\])", rest)] if rest.strip() else []
+        if not seeded and op.startswith("s_load_") and len(ops) >= 2:
+            karg |= _regs(ops[1])
+            seeded = True
+        if op.startswith("v_") and not op.startswith(_UNIFORM_SKIP) and len(ops) >= 2:
+            if not any(_VREG.search(o) for o in ops[1:]):
+                uniform.append(ins)
+        if op.startswith("global_load_") and len(ops) >= 2 and any(r in karg for o in ops[1:] for r in _regs(o)):
+            kload.append(ins)
+        if not ops:
+            continue
+        # follow the address: destination tainted iff a source is (loads return data, not addresses)
+        dst = _regs(ops[0])
+        if op.startswith("v_writelane") and len(ops) == 3:
+            slot = (ops[0], ops[2])
+            (karg.add if _regs(ops[1]) & karg else karg.discard)(slot)
+            continue
+        if op.startswith("v_readlane") and len(ops) == 3:
+            src = (ops[1], ops[2]) in karg
+        elif op.startswith(("s_load", "global_load", "buffer_load", "scratch_load", "ds_read", "s_waitcnt", "s_cbranch",
+                            "s_branch", "global_store", "scratch_store", "buffer_store", "ds_write", "s_cmp", "v_cmp")):
+            src = False
+            if "store" in op or op.startswith(("ds_write", "s_cmp", "v_cmp", "s_cbranch", "s_branch", "s_waitcnt")):
+                continue
+        else:
+            src = any(r in karg for o in ops[1:] for r in _regs(o))
+        for r in dst:
+            (karg.add if src else karg.discard)(r)
+    return uniform, kload
+
+
+_BODIES: dict[tuple, dict[str, list[str]]] = {}
+
+
+def render_bodies(lib: str) -> dict[str, list[str]]:
+    """{mangled k_render name: its instructions} from the gfx950 disassembly of ``lib``
+    (kept per library file and modification time: two guards read it)."""
+    key = (os.path.abspath(lib), os.path.getmtime(lib), os.path.getsize(lib))
+    if key not in _BODIES:
+        out: dict[str, list[str]] = {}
+        with tempfile.TemporaryDirectory() as d:
+            for co in code_objects(lib, d):
+                txt = subprocess.run([_tool("llvm-objdump"), "-d", "--no-show-raw-insn", co], check=True,
+                                     capture_output=True, text=True).stdout
+                out.update({n: b for n, b in asm_kernels(txt).items() if render_params(n)})
+        _BODIES.clear()
+        _BODIES[key] = out
+    return _BODIES[key]
+
+
+def uniform_valu(lib: str, stats: bool = False) -> dict[str, tuple[int, int]]:
+    """{mangled k_render name: (uniform VALU instructions, kernarg-derived global loads)} of the
+    timed render kernels in ``lib``, with ``stats`` of the counting ones too (uniform_scan over
+    the gfx950 disassembly)."""
+    return {name: tuple(len(x) for x in uniform_scan(body)) for name, body in render_bodies(lib).items()
+            if stats or not render_params(name)[1]}
+
+
+def scratch_ops(lib: str) -> dict[str, int]:
+    """{mangled k_render name: scratch_* instructions in its code} of every render kernel in ``lib``."""
+    return {name: sum(1 for i in body if i.startswith("scratch_")) for name, body in render_bodies(lib).items()}
+
+
+def check_uniform(lib: str) -> list[str]:
+    """The UNIFORM_VALU_LIMITS violations of ``lib``'s timed render kernels."""
+    bad = []
+    for name, (u, k) in sorted(uniform_valu(lib).items()):
+        p = render_params(name)
+        if p[1] == 1 or p[3] not in UNIFORM_VALU_LIMITS:
+            continue
+        lu, lk = UNIFORM_VALU_LIMITS[p[3]]
+        if u > lu or k > lk:
+            bad.append(f"k_render{p}: {u} wave-uniform VALU instructions (limit {lu}), {k} loads indexed into the "
+                       f"kernel arguments (limit {lk}): tools/isa_uniform.py lists them")
+    return bad
+
+
 def check(lib: str) -> dict[str, dict[str, int]]:
     """Raise if a render kernel copies its arguments to scratch or loses occupancy."""
     ks = kernels(lib)
@@ -221,6 +365,12 @@ def check(lib: str) -> dict[str, dict[str, int]]:
     for name in render:
         if modes.get(name, {}).get("dx10_clamp") != 1:
             bad.append(f"{name}: DX10_CLAMP is not set in the kernel descriptor ({modes.get(name)})")
+    # the counting kernels touch no scratch (their private segment, if any, is the unused slot
+    # of an SGPR tuple spilled to lanes: STATS_SCRATCH_LIMIT)
+    for name, n in scratch_ops(lib).items():
+        if render_params(name)[1] == 1 and n:
+            bad.append(f"{name}: {n} scratch instructions in a counting (STATS) kernel")
+    bad += check_uniform(lib)
     for p, (loops, n) in hot_loop_spills(lib).items():
         if not loops:
             bad.append(f"k_render{p}: no march / primary loop found in the disassembly (check the parser)")
