@@ -38,7 +38,10 @@ extern "C" {
  * Still ABI 10, additive only: the ray queries (vx_query_rays, vx_pixel_ray,
  * vx_place_rays and their structs) change no existing signature or layout.
  * Still ABI 10, additive only: supersampled antialiasing (vx_render_aa,
- * vx_aa_plan_for, vx_aa_plan) changes no existing signature or layout. */
+ * vx_aa_plan_for, vx_aa_plan) changes no existing signature or layout.
+ * Still ABI 10, additive only: the frame's depth and surface planes
+ * (vx_render_gbuffer, vx_gbuffer_planes, VX_SURF_*) change no existing signature
+ * or layout. */
 #define VX_ABI_VERSION 10
 
 /* error codes */
@@ -418,6 +421,78 @@ typedef struct vx_query_stats {
  * serialised per scene by the caller, and synchronise the stream. */
 int vx_query_rays(vx_scene *scene, const vx_ray *rays, int n, vx_ray_hit *hits,
                   int on_device, void *stream, vx_query_stats *stats);
+
+/* --- the frame's depth and surface planes (DESIGN.md "Frame G-buffer") --------
+ * The reference draws through GL, so its host has the frame's depth buffer;
+ * its README wants it for the labels ("as I haven't depth-culled them yet").
+ * vx_render_gbuffer gives a host that shows vx_render's frame the per-pixel
+ * depth and surface identity of that frame: to draw markers, routes and labels
+ * over it with correct occlusion, to outline where depth, normal or colour
+ * breaks, and to tell what is under the cursor.
+ *
+ * Definition, in terms of the ray queries above: let R be the vx_ray_hit that
+ * vx_query_rays returns for vx_pixel_ray(p, w, h, x, y) (t_max = INFINITY).
+ * Planes are w*h values, row-major, top row first.
+ *   depth[x, y]        = R.s[0].t if R.n >= 1, else +INFINITY: the nearest
+ *                        fragment, a glass pane included -- what the
+ *                        reference's depth buffer holds after the frame (depth
+ *                        writes are on for glass, render.js:82-91).
+ *   opaque_depth[x, y] = the t of R's record with id == 0, else +INFINITY: what
+ *                        a label hides behind; glass hides nothing, as in
+ *                        vx_place_rays' rule.
+ *   surface[x, y]      = one packed word (VX_SURF_* below): bits 0-1 R.n, bits
+ *                        2-4 normal_idx and bits 8-15 color of s[0], bits 18-20
+ *                        normal_idx and bits 24-31 color of the opaque record;
+ *                        every other bit 0, and the whole word 0 on a miss.  For
+ *                        n = 1 opaque both halves name the same record; for
+ *                        glass over sky the opaque half is 0.
+ * A pixel whose ray vx_query_rays would answer with VX_RAY_INVALID (an all-zero
+ * or non-finite direction, e.g. where fwd + nx*right + ny*up overflows) is
+ * written as a miss and counted in stats.invalid.
+ *
+ * What t means: the ray parameter in units of d = fwd + nx*right + ny*up (not
+ * normalised).  For a frame from vx_frame_from_orbit or vx_frame_from_matrix,
+ * fwd is unit along the eye axis and right, up are perpendicular to it, so t is
+ * the eye-space depth of the hit: the quantity vx_place_view.w holds for a
+ * place (compare the two directly: a place is behind the pixel's surface iff
+ * opaque_depth < view.w).  GL window depth for math.js:37-42's projection
+ * (near 1, far F; z_ndc = ((1 + F) - 2 F / t) / (F - 1)):
+ *   window_z = (z_ndc + 1) / 2 = F * (t - 1) / (t * (F - 1)),
+ * 0 at t = 1 and 1 at t = F.
+ *
+ * Only the camera (cam_cell, cam_fract), the ray basis (ray_fwd, ray_right,
+ * ray_up) and quality are read; every other field of p is ignored, flags
+ * included.  quality == 0 is VX_EINVAL: the 2D frame draws another mesh.  The
+ * walk always runs to its end, whichever planes are asked for: stats.fetches
+ * equals vx_query_rays' count for the same rays.  stats: rays = w*h, the rest as
+ * vx_query_rays counts them; vx_render's serialisation rule holds (a call with
+ * stats shares the scene's counters and events and synchronises the stream).
+ *
+ * out: any plane may be NULL (not wanted), not all three.  out_on_device != 0:
+ * device pointers on the scene's GPU, 4-byte aligned; the call is
+ * stream-ordered and does not synchronise; two planes that overlap are
+ * undefined.  Otherwise host arrays: the call stages them through a
+ * stream-ordered allocation on `stream`, copies back and synchronises that
+ * stream only.  stream NULL: the scene's own.  The call takes no scene lock and
+ * keeps no stream handle; it reads only what vx_scene_create left behind, so it
+ * may run concurrently with vx_render* and vx_query_rays on other streams.
+ * VX_EINVAL before any GPU call: a NULL scene, params or out; all planes NULL; w
+ * or h outside 1..32768; w*h > VX_MAX_QUERY_RAYS; quality == 0; |cam_cell| >=
+ * 2^22 on an axis; a cam_fract outside [0, 1) (NaN included); a non-finite
+ * basis component; a misaligned device plane. */
+#define VX_SURF_N(word) ((word) & 3u)
+#define VX_SURF_NORMAL(word) (((word) >> 2) & 7u)
+#define VX_SURF_COLOR(word) (((word) >> 8) & 0xffu)
+#define VX_SURF_OPAQUE_NORMAL(word) (((word) >> 18) & 7u)
+#define VX_SURF_OPAQUE_COLOR(word) (((word) >> 24) & 0xffu)
+typedef struct vx_gbuffer_planes {   /* any plane may be NULL (not wanted), not all three */
+    float    *depth;         /* w*h fp32 */
+    float    *opaque_depth;  /* w*h fp32 */
+    uint32_t *surface;       /* w*h words */
+} vx_gbuffer_planes;
+int vx_render_gbuffer(vx_scene *scene, const vx_frame_params *p, int w, int h,
+                      const vx_gbuffer_planes *out, int out_on_device, void *stream,
+                      vx_query_stats *stats);
 
 /* --- one frame across the GPUs of a node (RCCL over xGMI) -----
  * Replaces nothing in the reference (one browser GPU); SURVEY §8(e).  One

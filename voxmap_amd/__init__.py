@@ -15,6 +15,7 @@ from .renderer import (Frame, MultiGPU, Scene, blob_encrypt, decode, field_build
 from ._abi import QueryStats, RAY_INVALID
 from ._abi import AA_DEFAULT_SCRATCH, AA_MAX
 from .renderer import aa_plan
+from .renderer import GBUFFER_PLANES, SURF_DTYPE, unpack_surface
 
 __all__ = [
     "Scene", "Frame", "FrameParams", "Stats", "VoxmapError", "lib", "make_frame", "frame_from_orbit",
@@ -26,4 +27,5 @@ __all__ = [
     "MultiGPU", "mgpu_unique_id", "mgpu_band_rows", "mgpu_bands", "mgpu_transfers", "vertex2d",
     "RAY_DTYPE", "HIT_DTYPE", "SURFACE_DTYPE", "PLACE_VIEW_DTYPE", "QueryStats", "RAY_INVALID", "pixel_ray",
     "place_rays", "hits_visible", "aa_plan", "AA_MAX", "AA_DEFAULT_SCRATCH",
+    "GBUFFER_PLANES", "SURF_DTYPE", "unpack_surface",
 ]

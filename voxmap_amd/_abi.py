@@ -136,6 +136,11 @@ class QueryStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class GbufferPlanes(C.Structure):
+    """vx_gbuffer_planes: where vx_render_gbuffer writes each plane; NULL = not wanted."""
+    _fields_ = [("depth", C.c_void_p), ("opaque_depth", C.c_void_p), ("surface", C.c_void_p)]
+
+
 class PlaceView(C.Structure):
     """vx_place_view: drawOverlay's projection of one place (map.js:117-137)."""
     _fields_ = [("ndc_x", C.c_float), ("ndc_y", C.c_float), ("w", C.c_float), ("distance", C.c_float),
@@ -189,6 +194,8 @@ SIGNATURES = [
     ("vx_field_build_gpu", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     ("vx_query_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                 C.POINTER(QueryStats)]),
+    ("vx_render_gbuffer", C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.c_int, C.c_int, C.POINTER(GbufferPlanes),
+                                    C.c_int, C.c_void_p, C.POINTER(QueryStats)]),
     ("vx_pixel_ray", C.c_int, [C.POINTER(FrameParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Ray)]),
     ("vx_place_rays", C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_void_p, C.c_int, C.c_void_p,
                                 C.c_void_p]),

@@ -85,6 +85,7 @@ struct vx_scene {
     bool f32_scene = false;       // the scene's half of the fp32-index predicate (do_render adds the camera's)
     KernelArgs ka;                // what no frame changes of do_render's arguments, filled once (scene_consts)
     QueryArgs qa;                 // and of do_query's
+    GbufArgs ga;                  // and of do_gbuffer's
 };
 
 #define VX_HIP(call)                                                                                 \
@@ -279,7 +280,7 @@ static hipError_t face_tables(vx_scene *s, const SceneInputs &in, Scratch &sc) {
 }
 
 // The launch arguments' fields that no frame changes, from zeroed structs
-// (padding stays zero): do_render and do_query copy them and add the frame's.
+// (padding stays zero): do_render, do_query and do_gbuffer copy them and add the frame's.
 static void scene_consts(vx_scene *s) {
     KernelArgs &a = s->ka;
     std::memset(&a, 0, sizeof a);
@@ -310,6 +311,11 @@ static void scene_consts(vx_scene *s) {
     q.X = s->X; q.Y = s->Y; q.Z = s->Z;
     q.pad = a.pad; q.Xp = a.Xp; q.Xpf = a.Xpf; q.XpYp = a.XpYp;
     q.copy_texels = a.copy_texels;
+    GbufArgs &g = s->ga;
+    std::memset(&g, 0, sizeof g);
+    g.prim = a.prim;
+    g.Xpf = a.Xpf; g.XpYp = a.XpYp; g.copy_texels = a.copy_texels;
+    g.cap = 4 * (s->X + s->Y + s->Z);
 }
 
 // the scene's device half; the scratch buffers go after the final stream synchronisation
@@ -619,6 +625,16 @@ static int do_render(vx_scene *s, const vx_frame_params *p, int w, int h, const 
     return VX_OK;
 }
 
+static void fill_query_stats(vx_query_stats *st, uint64_t rays, const unsigned long long *v, float ms) {
+    st->rays = rays;
+    st->invalid = v[QS_INVALID];
+    st->hits = v[QS_HITS];
+    st->glass = v[QS_GLASS];
+    st->fetches = v[QS_FETCH];
+    st->cap_hits = v[QS_CAP_HITS];
+    st->kernel_ms = ms;
+}
+
 // One k_query launch over device arrays.  It reads only what vx_scene_create
 // left behind (the octant copies and their layout), so it takes no scene lock;
 // with stats it uses the scene's counters and events, as a vx_render with stats.
@@ -636,13 +652,31 @@ static int do_query(vx_scene *s, const void *d_rays, int n, void *d_hits, hipStr
         unsigned long long v[QS_COUNT];
         float ms = 0.0f;
         VX_CHECK(stats_end(s, v, QS_COUNT, st, &ms));
-        stats->rays = (uint64_t)n;
-        stats->invalid = v[QS_INVALID];
-        stats->hits = v[QS_HITS];
-        stats->glass = v[QS_GLASS];
-        stats->fetches = v[QS_FETCH];
-        stats->cap_hits = v[QS_CAP_HITS];
-        stats->kernel_ms = ms;
+        fill_query_stats(stats, (uint64_t)n, v, ms);
+    }
+    return VX_OK;
+}
+
+// One k_gbuffer launch into device planes.  As do_query: it reads only what
+// vx_scene_create left behind, takes no scene lock and keeps no stream handle;
+// with stats it uses the scene's counters and events.
+static int do_gbuffer(vx_scene *s, const vx_frame_params *p, int w, int h, const vx_gbuffer_planes &d, hipStream_t st,
+                      vx_query_stats *stats) {
+    GbufArgs a;
+    std::memcpy(&a, &s->ga, sizeof a);
+    gbuffer_frame(*p, w, h, s->X, s->Y, s->Z, s->L.pad, a);
+    a.depth = d.depth; a.opaque_depth = d.opaque_depth; a.surface = d.surface;
+    if (stats) {
+        a.stats = s->d_stats.get();
+        VX_CHECK(stats_begin(s, QS_COUNT, st));
+    }
+    const int rc = launch_gbuffer(a, st);
+    if (rc) return set_error(VX_EDEVICE, std::string("gbuffer launch failed: ") + hipGetErrorString((hipError_t)rc));
+    if (stats) {
+        unsigned long long v[QS_COUNT];
+        float ms = 0.0f;
+        VX_CHECK(stats_end(s, v, QS_COUNT, st, &ms));
+        fill_query_stats(stats, (uint64_t)w * (uint64_t)h, v, ms);
     }
     return VX_OK;
 }
@@ -882,6 +916,48 @@ int vx_query_rays(vx_scene *s, const vx_ray *rays, int n, vx_ray_hit *hits, int 
     }
     if (d_r) (void)hipFreeAsync(d_r, st);
     if (d_h) (void)hipFreeAsync(d_h, st);
+    (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+int vx_render_gbuffer(vx_scene *s, const vx_frame_params *p, int w, int h, const vx_gbuffer_planes *out,
+                      int out_on_device, void *stream, vx_query_stats *stats) {
+    if (!s || !p || !out) return set_error(VX_EINVAL, "vx_render_gbuffer: null argument");
+    if (!out->depth && !out->opaque_depth && !out->surface)
+        return set_error(VX_EINVAL, "vx_render_gbuffer: no plane asked for");
+    VX_CHECK(check_frame_size(w, h));
+    if ((long long)w * h > VX_MAX_QUERY_RAYS)
+        return set_error(VX_EINVAL, "vx_render_gbuffer: w * h above VX_MAX_QUERY_RAYS (2^26)");
+    if (p->quality == 0)
+        return set_error(VX_EINVAL, "vx_render_gbuffer: quality 0 (the 2D frame) draws another mesh; no planes for it");
+    VX_CHECK(check_camera(p));
+    void *const planes[3] = {out->depth, out->opaque_depth, out->surface};
+    if (out_on_device)
+        for (void *q : planes)
+            if ((uintptr_t)q & 3u) return set_error(VX_EINVAL, "vx_render_gbuffer: device planes must be 4-byte aligned");
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    VX_HIP(hipSetDevice(s->device));
+    hipStream_t st = stream_of(s, stream);
+    if (out_on_device) return do_gbuffer(s, p, w, h, *out, st, stats);
+    // host planes: one stream-ordered allocation holds the wanted ones back to back
+    const size_t plane = (size_t)w * h * 4;
+    int wanted = 0;
+    for (void *q : planes) wanted += q ? 1 : 0;
+    void *d_all = nullptr;
+    VX_HIP(hipMallocAsync(&d_all, plane * wanted, st));
+    void *d_planes[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0, at = 0; k < 3; k++)
+        if (planes[k]) d_planes[k] = static_cast<char *>(d_all) + plane * at++;
+    const vx_gbuffer_planes dev = {(float *)d_planes[0], (float *)d_planes[1], (uint32_t *)d_planes[2]};
+    int rc = do_gbuffer(s, p, w, h, dev, st, stats);
+    if (rc == VX_OK) {
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < 3 && e == hipSuccess; k++)
+            if (planes[k]) e = hipMemcpyAsync(planes[k], d_planes[k], plane, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = set_error(VX_EDEVICE, std::string("gbuffer readback failed: ") + hipGetErrorString(e));
+    }
+    (void)hipFreeAsync(d_all, st);
     (void)hipStreamSynchronize(st);
     return rc;
 }

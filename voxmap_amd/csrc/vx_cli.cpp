@@ -13,6 +13,10 @@
 //                 [--dims X,Y,Z] [--size W,H] [--camera K0|K1|K2 | --orbit sx,sy,sz,rx,ry,rz]
 //                 [--hour H] [--time T] [--flags N] [--full] [--samples N] [--radius R]
 //                 [--frames N] [--device D] [--ranks N] [--aa N] [--out FILE.ppm|FILE.rgba]
+//                 [--gbuffer PREFIX]
+// --gbuffer PREFIX: the frame's planes (vx_render_gbuffer) as raw little-endian files of w*h
+// values, row-major, top row first: PREFIX.depth.f32, PREFIX.opaque.f32, PREFIX.surface.u32;
+// not with --ranks.
 // --aa N (1, 2 or 4): N x N samples per pixel resolved on the device (vx_render_aa), as the
 // page's canvas is antialiased (map.js:7); not with --ranks.
 // The key may also come from the VOXMAP_KEY environment variable (never a file in the repository).
@@ -69,7 +73,7 @@ std::vector<unsigned char> read_all(const std::string &path) {
 }  // namespace
 
 int main(int argc, char **argv) {
-    std::string map, noise, key, out, format = "auto";
+    std::string map, noise, key, out, gbuffer, format = "auto";
     int dims[3] = {1024, 256, 32}, w = 3840, h = 2160, frames = 1, device = 0, samples = 0, ranks = 0, aa = 0;
     double sbj[3] = {381.5, 128.1, 40.0}, rot[3] = {1.1, 0.0, 0.6};   // camera K1 (voxmap_amd/presets.py)
     double hour = 1.0, time = 123.0, radius = 0.03;
@@ -105,11 +109,13 @@ int main(int argc, char **argv) {
         else if (a == "--ranks") ranks = std::atoi(next());
         else if (a == "--aa") aa = std::atoi(next());
         else if (a == "--out") out = next();
+        else if (a == "--gbuffer") gbuffer = next();
         else if (a == "--help" || a == "-h") {
             std::printf("usage: vxrender --map FILE [--format bin|gz|blob|grid] [--key K] [--noise FILE] "
                         "[--dims X,Y,Z] [--size W,H] [--camera K0|K1|K2 | --orbit sx,sy,sz,rx,ry,rz] [--hour H] "
                         "[--time T] [--flags N] [--full] [--samples N] [--radius R] [--frames N] [--device D] "
-                        "[--ranks N] [--aa N] [--out FILE.ppm|FILE.rgba]\n(ABI version %d)\n", vx_abi_version());
+                        "[--ranks N] [--aa N] [--out FILE.ppm|FILE.rgba] [--gbuffer PREFIX]\n(ABI version %d)\n",
+                        vx_abi_version());
             return 0;
         } else die("unknown option " + a);
     }
@@ -117,6 +123,7 @@ int main(int argc, char **argv) {
     if (key.empty() && std::getenv("VOXMAP_KEY")) key = std::getenv("VOXMAP_KEY");
     if (ranks < 0 || ranks > 64) die("--ranks must be in 0..64");
     if (aa != 0 && ranks >= 1) die("--aa is not available with --ranks");
+    if (!gbuffer.empty() && ranks >= 1) die("--gbuffer is not available with --ranks");
 
     // --ranks N: fork the rank processes now, before anything touches the GPU
     int rank = 0, nranks = 1, uid_pipe[2] = {-1, -1};
@@ -239,6 +246,20 @@ int main(int argc, char **argv) {
             std::fwrite(rgba.data(), 1, rgba.size(), f);
         }
         std::fclose(f);
+    }
+    if (!gbuffer.empty()) {
+        const size_t n = (size_t)w * h;
+        std::vector<float> depth(n), opaque(n);
+        std::vector<uint32_t> surface(n);
+        const vx_gbuffer_planes planes = {depth.data(), opaque.data(), surface.data()};
+        check(vx_render_gbuffer(scene, &p, w, h, &planes, 0, stream, nullptr), "vx_render_gbuffer");
+        const struct { const char *ext; const void *data; } files[] = {
+            {".depth.f32", depth.data()}, {".opaque.f32", opaque.data()}, {".surface.u32", surface.data()}};
+        for (const auto &pl : files) {
+            const std::string path = gbuffer + pl.ext;
+            FILE *f = std::fopen(path.c_str(), "wb");
+            if (!f || std::fwrite(pl.data, 4, n, f) != n || std::fclose(f) != 0) die("cannot write " + path);
+        }
     }
     (void)hipFree(d_out);
     (void)hipStreamDestroy(stream);

@@ -181,6 +181,31 @@ void frame_consts(const vx_frame_params &p, int w, int h, int X, int Y, int Z, i
     }
 }
 
+// The frame's part of k_gbuffer's arguments (vx_internal.h GbufArgs): the view
+// ray's constants and the camera-derived values of the walk, by frame_consts'
+// expressions above -- which are k_query's per-ray ones for the origin
+// (cam_cell, cam_fract).
+void gbuffer_frame(const vx_frame_params &p, int w, int h, int X, int Y, int Z, int pad, GbufArgs &a) {
+    for (int i = 0; i < 3; i++) {
+        a.fwd[i] = p.ray_fwd[i];
+        a.right[i] = p.ray_right[i];
+        a.up[i] = p.ray_up[i];
+        a.o[i] = p.cam_fract[i];
+        const int dim = i == 0 ? X : (i == 1 ? Y : Z);
+        a.slab_lo[i] = (float)(0 - p.cam_cell[i]) - p.cam_fract[i];
+        a.slab_hi[i] = (float)(dim - p.cam_cell[i]) - p.cam_fract[i];
+        a.cell_lo[i] = (float)(-p.cam_cell[i]);
+        a.cell_hi[i] = (float)(dim - p.cam_cell[i] - 1);
+        a.padded[i] = (float)(p.cam_cell[i] + pad);
+    }
+    a.w = w;
+    a.h = h;
+    a.fw = (float)w;
+    a.fh = (float)h;
+    a.rcp_w = 1.0f / a.fw;
+    a.rcp_h = 1.0f / a.fh;
+}
+
 }  // namespace vx
 
 namespace vx {

@@ -146,16 +146,23 @@ int vx::scene_inputs(const vx_scene_desc *d, SceneInputs &in) {
     return VX_OK;
 }
 
-int vx::check_frame(const vx_frame_params *p, int w, int h, int fmt) {
-    if (!p) return set_error(VX_EINVAL, "null scene/params");
+int vx::check_frame_size(int w, int h) {
     if (w <= 0 || h <= 0 || w > 32768 || h > 32768) return set_error(VX_EINVAL, "frame size out of range");
-    if (fmt != VX_PIXEL_RGBA32F && fmt != VX_PIXEL_RGBA8) return set_error(VX_EINVAL, "unknown pixel format");
+    return VX_OK;
+}
+
+static int check_finite3(const char *name, const float *v) {
+    for (int i = 0; i < 3; i++)
+        if (!std::isfinite(v[i])) return set_error(VX_EINVAL, std::string("non-finite frame parameter ") + name);
+    return VX_OK;
+}
+
+int vx::check_camera(const vx_frame_params *p) {
+    if (!p) return set_error(VX_EINVAL, "null scene/params");
     const struct { const char *name; const float *v; } vec[] = {
-        {"cam_fract", p->cam_fract}, {"ray_fwd", p->ray_fwd}, {"ray_right", p->ray_right}, {"ray_up", p->ray_up},
-        {"sun_dir", p->sun_dir}};
+        {"cam_fract", p->cam_fract}, {"ray_fwd", p->ray_fwd}, {"ray_right", p->ray_right}, {"ray_up", p->ray_up}};
     for (const auto &f : vec)
-        for (int i = 0; i < 3; i++)
-            if (!std::isfinite(f.v[i])) return set_error(VX_EINVAL, std::string("non-finite frame parameter ") + f.name);
+        if (const int rc = check_finite3(f.name, f.v)) return rc;
     // u_fractPos is fract(position) (render.js:289-290); the primary traversal
     // relies on 0 <= o < 1 and on camera-relative cells below 2^22
     for (int i = 0; i < 3; i++) {
@@ -164,6 +171,15 @@ int vx::check_frame(const vx_frame_params *p, int w, int h, int fmt) {
         if (p->cam_cell[i] <= -(1 << 22) || p->cam_cell[i] >= (1 << 22))
             return set_error(VX_EINVAL, "cam_cell out of range (|cell| < 2^22)");
     }
+    return VX_OK;
+}
+
+int vx::check_frame(const vx_frame_params *p, int w, int h, int fmt) {
+    if (!p) return set_error(VX_EINVAL, "null scene/params");
+    if (const int rc = check_frame_size(w, h)) return rc;
+    if (fmt != VX_PIXEL_RGBA32F && fmt != VX_PIXEL_RGBA8) return set_error(VX_EINVAL, "unknown pixel format");
+    if (const int rc = check_camera(p)) return rc;
+    if (const int rc = check_finite3("sun_dir", p->sun_dir)) return rc;
     if (p->shadow_samples > VX_MAX_SHADOW_SAMPLES)
         return set_error(VX_EINVAL, "shadow_samples must be <= VX_MAX_SHADOW_SAMPLES (16)");
     if (p->shadow_samples > 1 && !(p->sun_radius >= 0.0f && p->sun_radius <= 0.5f))

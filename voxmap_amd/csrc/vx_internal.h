@@ -163,8 +163,12 @@ struct SceneInputs {
     std::vector<unsigned char> field, noise;
 };
 int scene_inputs(const vx_scene_desc *d, SceneInputs &in);
-// vx_render*'s frame checks (vx_host.cpp)
+// vx_render*'s frame checks (vx_host.cpp), and the two pieces of them that
+// vx_render_gbuffer shares: the frame size (1 .. 32768 a side) and the camera
+// (cam_fract in [0, 1), |cam_cell| < 2^22, a finite ray basis)
 int check_frame(const vx_frame_params *p, int w, int h, int fmt);
+int check_frame_size(int w, int h);
+int check_camera(const vx_frame_params *p);
 // padded int8 sun channels (border = -1) from the linear RGBA upload
 int launch_sun_pad(const uint32_t *lin, int8_t *sunp, int X, int Y, int Z, int SB, void *stream);
 // Sun exit tables (DESIGN.md §3 "Sun exit tables"): copies of sunp's march
@@ -251,6 +255,31 @@ struct QueryArgs {
 };
 enum QueryStatSlot { QS_INVALID = 0, QS_HITS, QS_GLASS, QS_FETCH, QS_CAP_HITS, QS_COUNT };
 int launch_query(const QueryArgs &a, void *stream);
+
+// Parameters of one frame G-buffer launch (vx_gbuffer.hip; by value, about fifty
+// words).  The scene's part is filled once (scene_consts), the frame's by
+// gbuffer_frame with the fp32 operations frame_consts performs for FrameConsts:
+// the origin is the camera, the same for every pixel, so what k_query derives
+// per ray from its origin arrives here as wave-uniform values.
+struct GbufArgs {
+    const uint32_t *prim;    // the 8 padded octant copies (KernelArgs::prim)
+    float *depth;            // w*h planes, each may be null (not wanted)
+    float *opaque_depth;
+    uint32_t *surface;
+    unsigned long long *stats;   // QS_COUNT device counters, or nullptr
+    float Xpf;               // (float)FieldLayout::Xp
+    unsigned XpYp, copy_texels;
+    int cap;                 // the walk's iteration cap, 4 * (X + Y + Z)
+    int w, h;
+    // view_ray's constants, named as FrameConsts names them
+    float fwd[3], right[3], up[3];
+    float fw, fh, rcp_w, rcp_h;
+    float o[3];              // cam_fract
+    float slab_lo[3], slab_hi[3], cell_lo[3], cell_hi[3];   // as FrameConsts'
+    float padded[3];         // (float)(cam_cell + pad): exact, |cam_cell| < 2^22 and pad = cap <= 256
+};
+void gbuffer_frame(const vx_frame_params &p, int w, int h, int X, int Y, int Z, int pad, GbufArgs &a);
+int launch_gbuffer(const GbufArgs &a, void *stream);
 
 // Launchers (vx_dispatch.hip).  Return a hipError_t as int.
 int launch_render(const KernelArgs &a, int pixel_format, void *stream);

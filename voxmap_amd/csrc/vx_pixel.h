@@ -60,7 +60,9 @@ __device__ __forceinline__ size_t out_index(const KernelArgs &a, int k, int x, i
 }
 
 // view ray of pixel (px, py): nx = (2px+1)/w - 1, ny = 1 - (2py+1)/h with exact quotients
-__device__ __forceinline__ void view_ray(const FrameConsts &F, int px, int py, float &d0, float &d1, float &d2) {
+// (FC: FrameConsts, or GbufArgs, which carries the same seven constants under the same names)
+template <class FC>
+__device__ __forceinline__ void view_ray(const FC &F, int px, int py, float &d0, float &d1, float &d2) {
     const float nx = div_const((float)(2 * px + 1), F.fw, F.rcp_w) - 1.0f;
     const float ny = 1.0f - div_const((float)(2 * py + 1), F.fh, F.rcp_h);
     d0 = (F.fwd[0] + nx * F.right[0]) + ny * F.up[0];

@@ -129,6 +129,33 @@ def hits_visible(hits: np.ndarray) -> np.ndarray:
     return ~hidden
 
 
+# ---- the frame's planes (vx_render_gbuffer) ----
+GBUFFER_PLANES = ("depth", "opaque_depth", "surface")
+_PLANE_DTYPE = {"depth": np.float32, "opaque_depth": np.float32, "surface": np.uint32}
+SURF_DTYPE = np.dtype([("n", np.uint8), ("normal_idx", np.uint8), ("color", np.uint8),
+                       ("opaque_normal_idx", np.uint8), ("opaque_color", np.uint8)])
+
+
+def unpack_surface(words) -> np.ndarray:
+    """The fields of vx_render_gbuffer's surface words (VX_SURF_N, _NORMAL, _COLOR, _OPAQUE_NORMAL,
+    _OPAQUE_COLOR of include/voxmap.h) as a SURF_DTYPE array of the words' shape."""
+    w = np.asarray(words, dtype=np.uint32)
+    out = np.zeros(w.shape, SURF_DTYPE)
+    out["n"] = w & 3
+    out["normal_idx"] = (w >> 2) & 7
+    out["color"] = (w >> 8) & 0xFF
+    out["opaque_normal_idx"] = (w >> 18) & 7
+    out["opaque_color"] = (w >> 24) & 0xFF
+    return out
+
+
+def _plane_names(planes) -> tuple:
+    names = tuple(planes)
+    if not names or len(set(names)) != len(names) or any(n not in GBUFFER_PLANES for n in names):
+        raise ValueError(f"planes: a non-empty selection of {GBUFFER_PLANES}, got {names}")
+    return names
+
+
 class Scene:
     """Device-resident field + noise textures on one GPU (render.js:134-206)."""
 
@@ -319,6 +346,29 @@ class Scene:
         st = _abi.QueryStats() if stats else None
         check(lib().vx_query_rays(self.handle, C.c_void_p(rays_ptr), int(n), C.c_void_p(hits_ptr), 1,
                                   C.c_void_p(stream) if stream else None, C.byref(st) if st is not None else None))
+        return st
+
+    def gbuffer(self, frame: Frame, planes=GBUFFER_PLANES, stats: bool = False):
+        """The frame's depth and surface planes (vx_render_gbuffer) to host memory: a dict of
+        (h, w) arrays, float32 ``depth`` / ``opaque_depth`` and uint32 ``surface`` words
+        (unpack_surface), for the names in ``planes``; with ``stats`` also the call's QueryStats."""
+        w, h = frame.width, frame.height
+        out = {n: np.empty((h, w), _PLANE_DTYPE[n]) for n in _plane_names(planes)}
+        st = self._gbuffer(frame, {n: a.ctypes.data for n, a in out.items()}, 0, None, stats)
+        return (out, st) if stats else out
+
+    def gbuffer_device(self, frame: Frame, *, depth: int = 0, opaque_depth: int = 0, surface: int = 0, stream=None,
+                       stats: bool = False):
+        """vx_render_gbuffer into device planes given as raw pointers (e.g. torch tensors' data_ptr();
+        0 = not wanted): stream-ordered, no synchronisation unless ``stats``."""
+        return self._gbuffer(frame, {"depth": depth, "opaque_depth": opaque_depth, "surface": surface}, 1, stream, stats)
+
+    def _gbuffer(self, frame: Frame, ptrs: dict, on_device: int, stream, stats: bool):
+        pl = _abi.GbufferPlanes(*(ptrs.get(n) or None for n in GBUFFER_PLANES))
+        st = _abi.QueryStats() if stats else None
+        check(lib().vx_render_gbuffer(self.handle, C.byref(frame.params), frame.width, frame.height, C.byref(pl),
+                                      on_device, C.c_void_p(stream) if stream else None,
+                                      C.byref(st) if st is not None else None))
         return st
 
     def pick(self, frame: Frame, px: int, py: int):
