@@ -597,6 +597,16 @@ static int do_render(vx_scene *s, const vx_frame_params *p, int w, int h, const 
     a.kx4 = (float)(4 * (p->cam_cell[0] + a.pad));
     a.ky = (float)(p->cam_cell[1] + a.pad);
     a.kz = 4u * a.XpYp * (unsigned)(p->cam_cell[2] + a.pad);
+    // the octant terms of that offset, one scalar per sign a lane's compare selects
+    // (primary(): 0x4B000000 and 4*XpYp << 22 are the biases of its x/y sum and its z)
+    {
+        const unsigned XpYp4 = 4u * a.XpYp, kzb = a.kz - 0x4B000000u - (XpYp4 << 22);
+        a.kx4b = a.kx4 + 8388608.0f;
+        a.kz_neg = kzb + (a.copy_texels << 4);
+        a.kz_up = 0u - (a.copy_texels << 4) - XpYp4;
+        a.koct0 = a.copy_texels << 2;
+        a.koct1 = a.copy_texels << 3;
+    }
 #ifdef VX_BLOCK_TIMING
     if (!ts.ids) {
         const size_t nb = (size_t)((w + 31) / 32) * (size_t)((h + 7) / 8);

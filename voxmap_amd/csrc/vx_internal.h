@@ -131,6 +131,11 @@ struct KernelArgs {
     int prim_f32;            // 0: the integer index path
     float kx4, ky;           // 4*(camera padded x), camera padded y (ray octant terms added per lane)
     unsigned kz;             // 4*XpYp*(camera padded z), mod 2^32
+    // the same index's per-lane octant terms as scalars a sign compare selects (primary(); all mod 2^32)
+    float kx4b;              // kx4 + 2^23: the x/y sum's bias folded in (a multiple of 4 below 2^25: exact)
+    unsigned kz_neg;         // kz less both bias constants, for a ray going down z (plus 16*copy_texels: octant bit 2)
+    unsigned kz_up;          // what a ray going up z adds to kz_neg: -(16*copy_texels) - 4*XpYp
+    unsigned koct0, koct1;   // 4*copy_texels, 8*copy_texels: the byte offsets of octant bits 0 and 1
 };
 
 // tile sizes must be multiples of the render kernel's block (32 x 8 pixels)

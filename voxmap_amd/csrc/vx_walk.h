@@ -38,6 +38,20 @@ __device__ __forceinline__ void qcopy_offsets(uint32_t w, int ax, float &o0, flo
     uv_offsets(ax, (float)(q & 31u), (float)(q >> 5), o0, o1, o2);
 }
 
+// qcopy_offsets with the axis given as its field's shift (0, 10, 20) and as the
+// float masks m_i = (ax == i ? 1 : 0): each offset is the sum of two products
+// of which at most one is non-zero, lo and hi are integers 0..31 and the masks
+// 0 or 1, so every product and the sum are exact, and a zero is +0 as the
+// select form's (no factor is negative).
+__device__ __forceinline__ void qcopy_place(uint32_t w, unsigned sh, float m0, float m1, float m2, float &o0, float &o1,
+                                            float &o2) {
+    const unsigned q = w >> sh;
+    const float lo = (float)(q & 31u), hi = (float)((q >> 5) & 31u);
+    o0 = __builtin_fmaf(hi, m1, lo * m2);
+    o1 = __builtin_fmaf(hi, m2, lo * m0);
+    o2 = __builtin_fmaf(hi, m0, lo * m1);
+}
+
 // iv = RN(1/d) (kInf for d = 0, a positive axis as -0 is) of a walk outside
 // primary(), which fuses its slab products into the fast branch: rcp_ranged is
 // exact for |d| in [2^-40, 2^41) -- every lane of nearly every wave; a wave with
@@ -135,24 +149,35 @@ __device__ __forceinline__ int primary(const KernelArgs &a, int oct, float d0, f
     const float cf1 = __builtin_amdgcn_fmed3f(floorf(o1 + tlo * d1), F.cell_lo[1], F.cell_hi[1]);
     const float cf2 = __builtin_amdgcn_fmed3f(floorf(o2 + tlo * d2), F.cell_lo[2], F.cell_hi[2]);
     const bool p0 = !(d0 < 0.0f), p1 = !(d1 < 0.0f), p2 = !(d2 < 0.0f);
-    const int ip0 = p0, ip1 = p1, ip2 = p2;
-    const float s0 = p0 ? 1.0f : -1.0f, s1 = p1 ? 1.0f : -1.0f, s2 = p2 ? 1.0f : -1.0f;
-    const float hp0 = p0 ? 1.0f : 0.0f, hp1 = p1 ? 1.0f : 0.0f, hp2 = p2 ? 1.0f : 0.0f;
+    // one select per axis: hp is exactly 1 or 0, so s = 2*hp - 1 is exactly +-1
+    // (the fma written out: its product 2*hp is exact, one rounding of an
+    // exact +-1 -- the select form's value, and never a zero)
+    float hp0 = p0 ? 1.0f : 0.0f, hp1 = p1 ? 1.0f : 0.0f, hp2 = p2 ? 1.0f : 0.0f;
+    asm volatile("" : "+v"(hp0), "+v"(hp1), "+v"(hp2));   // (or the compiler folds s back into a select of its own)
+    const float s0 = __builtin_fmaf(hp0, 2.0f, -1.0f), s1 = __builtin_fmaf(hp1, 2.0f, -1.0f),
+                s2 = __builtin_fmaf(hp2, 2.0f, -1.0f);
     float h0 = cf0 + hp0, h1 = cf1 + hp1, h2 = cf2 + hp2;
     // padded index of h: kray + hx + Xp*hy + XpYp*hz, mod 2^32 with 24-bit
-    // signed products (|h| < 2^23)
+    // signed products (|h| < 2^23); the octant's terms are scalars the sign
+    // compares select
     const uint32_t *ppad = a.prim + (size_t)oct * a.copy_texels;
-    const int kray = (int)a.kcam - ip0 - a.Xp * ip1 - (int)a.XpYp * ip2;
+    const int kray = (int)a.kcam - (p0 ? 1 : 0) - (p1 ? a.Xp : 0) - (p2 ? (int)a.XpYp : 0);
     // F32IDX (a.prim_f32): the byte offset 4*(x + Xp*y) in fp32 (exact, <
     // 2^23), z by a 24-bit multiply-add, 32 bits from a.prim, all without
     // float -> int converts: the x/y sum is biased by 2^23 (its bit pattern is
     // 0x4B000000 + the sum) and z by 2^23 + 2^22 (|z| < 2^21: the low 24 bits
-    // of the pattern are 2^22 + z); kz takes both constants back, mod 2^32
-    const float kx4 = a.kx4 - (float)(4 * ip0) + 8388608.0f, ky = a.ky - (float)ip1;
+    // of the pattern are 2^22 + z); kz takes both constants back, mod 2^32.
+    // The octant terms come from the host as scalars (KernelArgs::kx4b ..):
+    // kx4b - 4*hp0 has integer terms that are multiples of 4 below 2^25, so the
+    // fma's one rounding is exact, as the former two were; kz sums, mod 2^32,
+    // what the sign compares select of 4*copy_texels << bit per negative axis
+    // and of the z term (the former oct * copy_texels * 4 - 4*XpYp * ip2)
+    const float kx4 = __builtin_fmaf(hp0, -4.0f, a.kx4b), ky = a.ky - hp1;
     const float fXp4 = a.Xp4f;
     const unsigned XpYp4 = 4u * a.XpYp;
-    const unsigned kz = a.kz - XpYp4 * (unsigned)ip2 + (((unsigned)oct * a.copy_texels) << 2) - 0x4B000000u -
-                        (XpYp4 << 22);
+    // (each select has 0 for one arm: a select between two arguments becomes a
+    // load through a selected pointer into the kernel arguments)
+    const unsigned kz = a.kz_neg + ((p0 ? 0u : a.koct0) + (p1 ? 0u : a.koct1) + (p2 ? a.kz_up : 0u));
     // QSPEC (the fp32-index path, a.qcopy): every step also loads the cell's
     // entry-face quad offsets from a.qcopy at the same byte offset (the copy has
     // the prim layout), so the hit's offsets arrive with its colour instead of
@@ -206,8 +231,13 @@ __device__ __forceinline__ int primary(const KernelArgs &a, int oct, float d0, f
         col = t & 0xff;
         // a face of the mesh: entering a meshed cell (vis colour != 0) from a
         // cell of another colour; air is never meshed (sdf.cpp:229-233,284)
-        const bool enter = col != prev && col != 0;
-        if (enter && col == kGlass) {                  // a glass entry (rare, divergent)
+        // (enter = col != prev && col != 0.)  The lane's stop flag is enter &&
+        // col != kGlass -- later glass entries are passed, the stacked pass blends
+        // them -- as a value that is non-zero exactly then: the unsigned minimum
+        // of col ^ prev, col and col ^ kGlass, one 3-operand minimum in place of
+        // two compares and a select, tested once by the loop
+        const unsigned dprev = (unsigned)(col ^ prev), dglass = (unsigned)(col ^ kGlass);
+        if (dglass == 0 && dprev != 0) {               // a glass entry (rare, divergent)
             if (gmark == kGlass) {                     // the first: blend over the next surface
                 gmark = 256;
                 g0h = h0; g1h = h1; g2h = h2; gt = te;
@@ -217,7 +247,7 @@ __device__ __forceinline__ int primary(const KernelArgs &a, int oct, float d0, f
                 mul = 1;                               // a second pane in front of the surface
             }
         }
-        stop = (enter && col != kGlass) ? 1 : 0;       // later glass entries are passed (the stacked pass blends them)
+        stop = (int)min(min(dprev, (unsigned)col), dglass);
         asm volatile("" : "+v"(stop));                 // keep the lane flag in a VGPR
         prev = col;
         E0 = cvt_f32_ubyte1(t); E1 = cvt_f32_ubyte2(t); E2 = cvt_f32_ubyte3(t);
@@ -229,7 +259,11 @@ __device__ __forceinline__ int primary(const KernelArgs &a, int oct, float d0, f
     multi = mul;
     if (stop == 0) cnt.cap_hit++;
     const bool hit = stop != 0 && t < kSentinel;
-    const int hax = tb0 == te ? 0 : (tb1 == te ? 1 : 2);    // exit axis of the last step (ties x < y < z)
+    // exit axis of the last step (ties x < y < z), as the float masks m_i = 1 on
+    // it and 0 off it that place the record's values: m2 = (1 - m0) - m1, exact
+    const bool x0 = tb0 == te, x1 = !x0 && tb1 == te;
+    const int hax = x0 ? 0 : (x1 ? 1 : 2);
+    const float m0 = x0 ? 1.0f : 0.0f, m1 = x1 ? 1.0f : 0.0f, m2 = (1.0f - m0) - m1;
     // G-buffer records as the raster hands them over (render.vert:25-28):
     // v_cellPos = the origin of the greedy quad covering the face (the face
     // axis: its plane), v_fractPos = the hit point minus it, rounded once --
@@ -238,24 +272,31 @@ __device__ __forceinline__ int primary(const KernelArgs &a, int oct, float d0, f
     // tables are read before either record is formed.
     int nrec = 0;
     const bool gl = gmark != kGlass;
-    const bool gpos = gax == 0 ? p0 : (gax == 1 ? p1 : p2);
-    const bool hpos = hax == 0 ? p0 : (hax == 1 ? p1 : p2);
-    const float gr0 = g0h - hp0, gr1 = g1h - hp1, gr2 = g2h - hp2;   // relative cells
-    const float hr0 = h0 - hp0, hr1 = h1 - hp1, hr2 = h2 - hp2;
+    // the hit axis's hp (1: the ray goes up it), as the one non-zero product of
+    // 0/1 factors (exact), and the normal index 2*axis + hp as an exact small
+    // fp32 integer, converted once
+    const float hpf = __builtin_fmaf(m0, hp0, __builtin_fmaf(m1, hp1, m2 * hp2));
+    const int hnidx = (int)__builtin_fmaf(m2, 4.0f, __builtin_fmaf(m1, 2.0f, hpf));
+    const float hr0 = h0 - hp0, hr1 = h1 - hp1, hr2 = h2 - hp2;      // relative cells
     float gq0 = 0.0f, gq1 = 0.0f, gq2 = 0.0f, hq0 = 0.0f, hq1 = 0.0f, hq2 = 0.0f;
-    if (a.quad_gbuf) {
-        if (QSPEC) {
-            // the loaded entry-face word of the recorded step: 10 bits per face
-            // axis (the glass record's only in a wave that has one: most have none)
-            if (__ballot(gl) != 0) qcopy_offsets(gqw, gax, gq0, gq1, gq2);
-            qcopy_offsets(qw, hax, hq0, hq1, hq2);
-        } else {
-            if (gl) quad_offsets(a, gax, 2 * gax + (gpos ? 1 : 0), (int)gr0 + cc0, (int)gr1 + cc1, (int)gr2 + cc2, gq0, gq1, gq2);
-            if (hit) quad_offsets(a, hax, 2 * hax + (hpos ? 1 : 0), (int)hr0 + cc0, (int)hr1 + cc1, (int)hr2 + cc2, hq0, hq1, hq2);
+    if (QSPEC) {
+        // the loaded entry-face word of the recorded step, 10 bits per face axis
+        // (all zero with VX_FLAG_UNIT_GBUF: one AND with a scalar, no branch);
+        // the glass record's word is taken apart where that record is formed
+        qcopy_place(qw & (a.quad_gbuf ? ~0u : 0u), x0 ? 0u : (x1 ? 10u : 20u), m0, m1, m2, hq0, hq1, hq2);
+    } else if (a.quad_gbuf) {
+        if (gl) {
+            const bool gpos = gax == 0 ? p0 : (gax == 1 ? p1 : p2);
+            quad_offsets(a, gax, 2 * gax + (gpos ? 1 : 0), (int)(g0h - hp0) + cc0, (int)(g1h - hp1) + cc1,
+                         (int)(g2h - hp2) + cc2, gq0, gq1, gq2);
         }
+        if (hit) quad_offsets(a, hax, hnidx, (int)hr0 + cc0, (int)hr1 + cc1, (int)hr2 + cc2, hq0, hq1, hq2);
     }
     if (gl) {
+        const bool gpos = gax == 0 ? p0 : (gax == 1 ? p1 : p2);
         const float upf = gpos ? 0.0f : 1.0f;
+        const float gr0 = g0h - hp0, gr1 = g1h - hp1, gr2 = g2h - hp2;
+        if (QSPEC && a.quad_gbuf) qcopy_offsets(gqw, gax, gq0, gq1, gq2);
         const float r0 = gr0 - gq0, r1 = gr1 - gq1, r2 = gr2 - gq2;   // quad origin (exact small integers)
         g0.id = 2;
         g0.color = kGlass;
@@ -269,16 +310,21 @@ __device__ __forceinline__ int primary(const KernelArgs &a, int oct, float d0, f
         nrec = 1;
     }
     if (hit) {
-        const float upf = hpos ? 0.0f : 1.0f;
+        const float upf = 1.0f - hpf;                                  // 1 on a face entered going down its axis
         const float r0 = hr0 - hq0, r1 = hr1 - hq1, r2 = hr2 - hq2;
         const int id = col == kGlass ? 2 : 0;
-        const int nidx = 2 * hax + (hpos ? 1 : 0);
-        const float c0 = (r0 + F.cam_cell_f[0]) + (hax == 0 ? upf : 0.0f);
-        const float c1 = (r1 + F.cam_cell_f[1]) + (hax == 1 ? upf : 0.0f);
-        const float c2 = (r2 + F.cam_cell_f[2]) + (hax == 2 ? upf : 0.0f);
-        const float f0 = hax == 0 ? 0.0f : (o0 + te * d0) - r0;
-        const float f1 = hax == 1 ? 0.0f : (o1 + te * d1) - r1;
-        const float f2 = hax == 2 ? 0.0f : (o2 + te * d2) - r2;
+        const int nidx = hnidx;
+        // the face's plane: upf added on the hit axis alone.  upf * m_i is exactly
+        // +0 or 1 (both factors are), so the fma rounds (r + cam) + that once, as
+        // the select form's add did, with the same +0 off the axis
+        const float c0 = __builtin_fmaf(upf, m0, r0 + F.cam_cell_f[0]);
+        const float c1 = __builtin_fmaf(upf, m1, r1 + F.cam_cell_f[1]);
+        const float c2 = __builtin_fmaf(upf, m2, r2 + F.cam_cell_f[2]);
+        // (a select stays here: fma(-v, m, v) would turn v = -0 off the axis into
+        // +0, and v is -0 for cam_fract = -0 with te * d = -0, which the host admits)
+        const float f0 = x0 ? 0.0f : (o0 + te * d0) - r0;
+        const float f1 = x1 ? 0.0f : (o1 + te * d1) - r1;
+        const float f2 = (!x0 && !x1) ? 0.0f : (o2 + te * d2) - r2;
         // The record goes behind a glass record if the lane has one.  A wave
         // without any (nearly all: glass is 0.2 % of the headline frame's pixels)
         // writes g0 with no select per field; in the others every lane writes
