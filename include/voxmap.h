@@ -41,7 +41,9 @@ extern "C" {
  * vx_aa_plan_for, vx_aa_plan) changes no existing signature or layout.
  * Still ABI 10, additive only: the frame's depth and surface planes
  * (vx_render_gbuffer, vx_gbuffer_planes, VX_SURF_*) change no existing signature
- * or layout. */
+ * or layout.
+ * Still ABI 10, additive only: the sun queries (vx_query_sun, vx_ground_points
+ * and their structs) change no existing signature or layout. */
 #define VX_ABI_VERSION 10
 
 /* error codes */
@@ -493,6 +495,92 @@ typedef struct vx_gbuffer_planes {   /* any plane may be NULL (not wanted), not 
 int vx_render_gbuffer(vx_scene *scene, const vx_frame_params *p, int w, int h,
                       const vx_gbuffer_planes *out, int out_on_device, void *stream,
                       vx_query_stats *stats);
+
+/* --- sun queries: where the sun falls (DESIGN.md §3 "Sun queries") ------------
+ * The reference's sun moves every frame (map.js:399-402) and its field exists
+ * to accelerate the sun march (render.frag:75-142, used at :232-235), but a
+ * host can only see the result through a frame's pixels.  vx_query_sun answers
+ * for n points and k sun directions at once: which places are in the sun now,
+ * when a place gets sun today (k = a sweep of vx_sun_from_hour), a shade map of
+ * the whole field (the points of vx_ground_points).
+ *
+ * Definition.  lit(i, j) for point i and sun j is true iff both hold:
+ *   - the face test, when normal_idx >= 0: the frame's shadeFactor > 0
+ *     (render.frag:228-229) for the axis normal of normal_idx (render.vert:
+ *     14-17).  It fails iff suns[j][2] < 0.0f or the sun's component along that
+ *     normal is not > 0; such a pair is culled: unlit without a march, as the
+ *     frame skips the march at :232.  normal_idx == -1 culls nothing.
+ *   - march(cell, fract, suns[j]) of render.frag:75-142 ends with step ==
+ *     MAX_STEPS (:234).  MAX_STEPS = max_steps, <= 0 meaning 2*Z (the rule of
+ *     vx_frame_params.max_shadow_steps).
+ * suns is always a host array of k directions, as u_sunDir; they need not be
+ * normalised; it is uploaded stream-ordered per call.
+ *
+ * Output, point-major, VX_SUN_WORDS(k) words per point: word 0 = the number of
+ * suns that light the point (its "sun hours" for a sweep) or VX_SUN_INVALID;
+ * bit j & 31 of word 1 + j/32 = lit(i, j); bits at or past k are 0; for an
+ * invalid point every mask word is 0.
+ *
+ * The kernel checks every point itself and answers VX_SUN_INVALID without a
+ * march unless every cell axis lies inside the grid, every fract is finite
+ * with -1 <= f < 2, and normal_idx is in -1..5.  That range covers every
+ * record vx_query_rays returns (hit-point rounding puts fract a hair outside
+ * [0, 1)); it does not cover the quad-relative fracts of a default frame, whose
+ * first step can land far from cell.  No point makes the kernel read out of
+ * bounds (vx_sun_query.hip states the argument; it holds for the whole
+ * range above).  A query's march can start anywhere, so it reads
+ * copies of the march channels of its own, inside a border wide enough for a
+ * step whose axes tie: the scene's first vx_query_sun builds them on `stream`
+ * (about the memory of the frames' march copies once more) and later calls
+ * wait for that build's event; where they do not fit, the bounds-checked march
+ * runs instead.
+ *
+ * on_device != 0: points and out are device pointers on the scene's GPU
+ * (points 16-byte aligned, out 4-byte), the call is stream-ordered and does
+ * not synchronise.  Otherwise they are host arrays: the call stages them
+ * through stream-ordered allocations on `stream`, copies back and synchronises
+ * that stream only.  n == 0 does nothing.  VX_EINVAL before any GPU call: a
+ * NULL scene, points, suns or out; n < 0 or n > VX_MAX_QUERY_RAYS; k < 1 or k
+ * > VX_MAX_SUNS; a non-finite or all-zero sun; unknown flag bits; a misaligned
+ * device array.  stream NULL: the scene's own.  Calls may run concurrently on
+ * different streams of one scene, beside vx_render* and vx_query_rays; calls
+ * that ask for stats follow vx_render's rule: they share the scene's counters
+ * and events, are serialised per scene by the caller, and synchronise the
+ * stream.
+ *
+ * stats: points = n; rays = marches started, culled = pairs answered by the
+ * face test, rays + culled = (points - invalid) * k; lit = set mask bits;
+ * fetches = march texels read.  With VX_SUNQ_NO_EXIT the march reads the plain
+ * channel and fetches equals the reference's own count (every step of
+ * render.frag:92-136).  By default each sun's march reads the orthant exit copy
+ * of its octant where the scene has one (vx_prepare_sun's kind 1; never a cone
+ * copy, never a doom code): the same lit flags, fewer fetches. */
+#define VX_MAX_SUNS 1024
+#define VX_SUN_INVALID 0xFFFFFFFFu
+#define VX_SUN_WORDS(k) (1 + ((k) + 31) / 32)
+#define VX_SUNQ_NO_EXIT 0x1u       /* diagnostic: march the plain channel, every step of render.frag:92-136 */
+typedef struct vx_sun_point {      /* 32 bytes; device arrays 16-byte aligned */
+    int32_t cell[3];               /* as v_cellPos, unit-cell split (vx_surface.cell) */
+    float   fract[3];              /* as v_fractPos (vx_surface.fract) */
+    int32_t normal_idx;            /* 0..5: the face the point lies on (render.vert:14-17); -1: none */
+    uint32_t reserved;             /* 0 */
+} vx_sun_point;
+typedef struct vx_sun_stats {
+    uint64_t points, invalid, rays, culled, lit, fetches;
+    double kernel_ms;
+} vx_sun_stats;
+int vx_query_sun(vx_scene *scene, const vx_sun_point *points, int n, const float (*suns)[3], int k,
+                 int max_steps, uint32_t flags, uint32_t *out, int on_device, void *stream,
+                 vx_sun_stats *stats);
+/* The ground of a map.bin field as sun points (a pure host function, no GPU):
+ * for each column, x fastest, the top face of its topmost block (a block is R
+ * == G == 0, as the march sees it): cell = (x, y, ztop + 1), fract = (0.5,
+ * 0.5, 0), normal_idx = 4 (+z).  Columns with no block, or with ztop == Z - 1
+ * (no cell above it in the grid), are skipped.  columns[m] = x + X*y of emitted
+ * point m (may be NULL).  points == NULL: a size query (*n_out alone);
+ * otherwise cap, in points, must hold them all. */
+int vx_ground_points(const uint8_t *rgba_field, int X, int Y, int Z, vx_sun_point *points,
+                     int32_t *columns, size_t cap, size_t *n_out);
 
 /* --- one frame across the GPUs of a node (RCCL over xGMI) -----
  * Replaces nothing in the reference (one browser GPU); SURVEY §8(e).  One

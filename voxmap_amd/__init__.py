@@ -16,8 +16,12 @@ from ._abi import QueryStats, RAY_INVALID
 from ._abi import AA_DEFAULT_SCRATCH, AA_MAX
 from .renderer import aa_plan
 from .renderer import GBUFFER_PLANES, SURF_DTYPE, unpack_surface
+from ._abi import MAX_SUNS, SUN_INVALID, SUNQ_NO_EXIT, SunStats, sun_words
+from .renderer import SUN_POINT_DTYPE, ground_points, points_of_hits
 
 __all__ = [
+    "MAX_SUNS", "SUN_INVALID", "SUNQ_NO_EXIT", "SunStats", "sun_words", "SUN_POINT_DTYPE", "ground_points",
+    "points_of_hits",
     "Scene", "Frame", "FrameParams", "Stats", "VoxmapError", "lib", "make_frame", "frame_from_orbit",
     "frame_from_matrix", "sun_from_hour", "hour_from_time_ms", "field_build", "noise_synth", "decode",
     "blob_encrypt", "params_to_dict", "PIXEL_RGBA32F", "PIXEL_RGBA8", "FORMAT_AUTO", "FORMAT_BIN",

@@ -136,6 +136,29 @@ class QueryStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+MAX_SUNS = 1024
+SUN_INVALID = 0xFFFFFFFF
+SUNQ_NO_EXIT = 0x1                              # diagnostics: march the plain channel (the reference's own steps)
+
+
+def sun_words(k: int) -> int:
+    """VX_SUN_WORDS(k): the output words per point of vx_query_sun with k suns."""
+    return 1 + (int(k) + 31) // 32
+
+
+class SunPoint(C.Structure):
+    """vx_sun_point: cell + fract of a point, the face it lies on (-1: none)."""
+    _fields_ = [("cell", C.c_int32 * 3), ("fract", C.c_float * 3), ("normal_idx", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class SunStats(C.Structure):
+    _fields_ = [("points", C.c_uint64), ("invalid", C.c_uint64), ("rays", C.c_uint64), ("culled", C.c_uint64),
+                ("lit", C.c_uint64), ("fetches", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class GbufferPlanes(C.Structure):
     """vx_gbuffer_planes: where vx_render_gbuffer writes each plane; NULL = not wanted."""
     _fields_ = [("depth", C.c_void_p), ("opaque_depth", C.c_void_p), ("surface", C.c_void_p)]
@@ -196,6 +219,10 @@ SIGNATURES = [
                                 C.POINTER(QueryStats)]),
     ("vx_render_gbuffer", C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.c_int, C.c_int, C.POINTER(GbufferPlanes),
                                     C.c_int, C.c_void_p, C.POINTER(QueryStats)]),
+    ("vx_query_sun", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p,
+                               C.c_int, C.c_void_p, C.POINTER(SunStats)]),
+    ("vx_ground_points", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.POINTER(C.c_size_t)]),
     ("vx_pixel_ray", C.c_int, [C.POINTER(FrameParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Ray)]),
     ("vx_place_rays", C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_void_p, C.c_int, C.c_void_p,
                                 C.c_void_p]),

@@ -53,6 +53,17 @@ struct vx_scene {
     } cones[2];
     unsigned long long cone_tick = 0;
     std::mutex cone_mu;
+    // the sun queries' own march copies (sun_query_copies): sunp's two channels, then the orthant copies
+    // where the scene has them, inside a border of sun_query_border(Z) cells; built by the first vx_query_sun
+    struct SunQueryCopies {
+        int state = 0;                // 0: not tried yet, 1: built, -1: none (no padded copies, or they do not fit)
+        int SB = 0, SXp = 0, SYp = 0, SZp = 0;
+        bool exits = false;
+        DevBuf<int8_t> d;
+        Event ready;                  // recorded on the build's stream after the build
+        bool ready_seen = false;
+    } sunq;
+    std::mutex sunq_mu;
     // band / tile-id lists (vx_render_tiles / _bands, vx_detile), uploaded once
     // per distinct list and never rewritten while cached (list_acquire)
     struct ListBuf {
@@ -691,6 +702,84 @@ static int do_gbuffer(vx_scene *s, const vx_frame_params *p, int w, int h, const
     return VX_OK;
 }
 
+// The march copies a sun query reads, into the march's part of k: built on st by the scene's first
+// query (vx_sun_query.hip says why the frames' border does not serve), read by later ones on any stream
+// after the build's event.  A scene without padded copies, or one whose wide copies do not fit (memory,
+// or the march's 2^23 / 2^32 index limits of march_copies), gets none: k.sunp = nullptr, and every fast
+// sun takes the bounds-checked march_fast.
+static int sun_query_copies(vx_scene *s, hipStream_t st, KernelArgs &k) {
+    std::lock_guard<std::mutex> lock(s->sunq_mu);
+    vx_scene::SunQueryCopies &q = s->sunq;
+    if (q.state == 0) {
+        q.state = -1;
+        const int X = s->X, Y = s->Y, Z = s->Z, SB = sun_query_border(Z), ch = s->d_sunx ? 10 : 2;
+        const size_t sxy = (size_t)(X + 2 * SB) * (Y + 2 * SB), np = sxy * (size_t)(Z + 2 * SB);
+        if (s->d_sunp && sxy < (1u << 23) && sxy * (size_t)(Z + 2 * SB + 3) + 0x4B000000ull < (1ull << 32) &&
+            alloc_optional(q.d, (size_t)ch * np)) {
+            hipError_t e = q.ready.create(hipEventDisableTiming);
+            // d_sunp's two channels and d_sunx's eight are one run of channels each, in the same padded layout
+            if (e == hipSuccess) e = (hipError_t)launch_sun_widen(s->d_sunp.get(), q.d.get(), X, Y, Z, s->SB, SB, 2, st);
+            if (e == hipSuccess && ch == 10)
+                e = (hipError_t)launch_sun_widen(s->d_sunx.get(), q.d.get() + 2 * np, X, Y, Z, s->SB, SB, 8, st);
+            if (e == hipSuccess) e = hipEventRecord(q.ready.get(), st);
+            if (e != hipSuccess) {
+                (void)hipStreamSynchronize(st);
+                (void)q.d.reset();
+                return set_error(VX_EDEVICE, std::string("sun query copies: ") + hipGetErrorString(e));
+            }
+            q.SB = SB; q.SXp = X + 2 * SB; q.SYp = Y + 2 * SB; q.SZp = Z + 2 * SB;
+            q.exits = ch == 10;
+            q.state = 1;
+        }
+    }
+    k.sunc = nullptr;
+    if (q.state != 1) {
+        k.sunp = nullptr; k.sunx = nullptr;
+        return VX_OK;
+    }
+    VX_CHECK(wait_ready(q.ready.get(), q.ready_seen, st));
+    k.SB = q.SB; k.SBf = (float)q.SB; k.SXp = q.SXp; k.SXpf = (float)q.SXp;
+    k.SXpYp = (unsigned)q.SXp * (unsigned)q.SYp;
+    k.sunp_texels = k.SXpYp * (unsigned)q.SZp;
+    k.sunp = q.d.get();
+    k.sunx = q.exits ? q.d.get() + 2 * (size_t)k.sunp_texels : nullptr;
+    return VX_OK;
+}
+
+// One k_sun_query launch over device arrays (d_suns: the call's SunQ table).  As do_query: it reads
+// only what vx_scene_create and sun_query_copies left behind and keeps no stream handle; with stats
+// it uses the scene's counters and events.
+static int do_sun_query(vx_scene *s, const void *d_points, int n, const SunQ *d_suns, int k, int max_steps,
+                        uint32_t flags, uint32_t *d_out, hipStream_t st, vx_sun_stats *stats) {
+    SunQueryArgs a;
+    std::memset(&a, 0, sizeof a);
+    std::memcpy(&a.k, &s->ka, sizeof a.k);
+    VX_CHECK(sun_query_copies(s, st, a.k));
+    if (flags & VX_SUNQ_NO_EXIT) a.k.sunx = nullptr;
+    a.k.fc.max_steps = max_steps > 0 ? max_steps : 2 * s->Z;   // render.frag:12
+    a.points = d_points; a.out = d_out; a.suns = d_suns;
+    a.n = n; a.nsuns = k; a.words = VX_SUN_WORDS(k);
+    if (stats) {
+        a.stats = s->d_stats.get();
+        VX_CHECK(stats_begin(s, SS_COUNT, st));
+    }
+    const int rc = launch_sun_query(a, st);
+    if (rc) return set_error(VX_EDEVICE, std::string("sun query launch failed: ") + hipGetErrorString((hipError_t)rc));
+    if (stats) {
+        unsigned long long v[SS_COUNT];
+        float ms = 0.0f;
+        VX_CHECK(stats_end(s, v, SS_COUNT, st, &ms));
+        stats->points = (uint64_t)n;
+        stats->invalid = v[SS_INVALID];
+        stats->rays = v[SS_RAYS];
+        stats->culled = v[SS_CULLED];
+        stats->lit = v[SS_LIT];
+        stats->fetches = v[SS_FETCH];
+        stats->kernel_ms = ms;
+    }
+    return VX_OK;
+}
+
 // Chunks [c0, c1) of vx_render_aa's plan into their rows of the w x h device frame d_out:
 // chunk c is band c of the (ss*w) x (ss*h) frame at band height ss * chunk_rows_out,
 // rendered compact into `scratch` by the band path and resolved right behind it on st,
@@ -927,6 +1016,46 @@ int vx_query_rays(vx_scene *s, const vx_ray *rays, int n, vx_ray_hit *hits, int 
     if (d_r) (void)hipFreeAsync(d_r, st);
     if (d_h) (void)hipFreeAsync(d_h, st);
     (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+int vx_query_sun(vx_scene *s, const vx_sun_point *points, int n, const float (*suns)[3], int k, int max_steps,
+                 uint32_t flags, uint32_t *out, int on_device, void *stream, vx_sun_stats *stats) {
+    if (!s) return set_error(VX_EINVAL, "vx_query_sun: null scene");
+    VX_CHECK(check_sun_query(points, n, suns, k, flags, out, on_device));
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n == 0) return VX_OK;
+    VX_HIP(hipSetDevice(s->device));
+    hipStream_t st = stream_of(s, stream);
+    // the suns as the kernel reads them (sun_query_entry), uploaded stream-ordered per call.  The table is
+    // pageable host memory: hipMemcpyAsync returns once it has taken the source's bytes, so it may go with
+    // this call
+    std::vector<SunQ> table((size_t)k);
+    for (int j = 0; j < k; j++) sun_query_entry(suns[j], table[(size_t)j]);
+    const size_t qb = (size_t)k * sizeof(SunQ), pb = (size_t)n * sizeof(vx_sun_point),
+                 ob = (size_t)n * VX_SUN_WORDS(k) * sizeof(uint32_t);
+    void *d_q = nullptr, *d_p = nullptr, *d_o = nullptr;
+    int rc = VX_OK;
+    hipError_t e = hipMallocAsync(&d_q, qb, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_q, table.data(), qb, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && !on_device) {
+        e = hipMallocAsync(&d_p, pb, st);
+        if (e == hipSuccess) e = hipMallocAsync(&d_o, ob, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_p, points, pb, hipMemcpyHostToDevice, st);
+    }
+    if (e != hipSuccess) rc = set_error(VX_EDEVICE, std::string("sun query staging failed: ") + hipGetErrorString(e));
+    if (rc == VX_OK)
+        rc = do_sun_query(s, on_device ? points : d_p, n, static_cast<const SunQ *>(d_q), k, max_steps, flags,
+                          on_device ? out : static_cast<uint32_t *>(d_o), st, stats);
+    if (rc == VX_OK && !on_device) {
+        e = hipMemcpyAsync(out, d_o, ob, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = set_error(VX_EDEVICE, std::string("sun query readback failed: ") + hipGetErrorString(e));
+    }
+    if (d_q) (void)hipFreeAsync(d_q, st);
+    if (d_p) (void)hipFreeAsync(d_p, st);
+    if (d_o) (void)hipFreeAsync(d_o, st);
+    if (!on_device || rc != VX_OK) (void)hipStreamSynchronize(st);
     return rc;
 }
 

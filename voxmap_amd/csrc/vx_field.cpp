@@ -259,3 +259,33 @@ extern "C" int vx_vertex2d(const uint8_t *rgba, int X, int Y, int Z, void *out, 
     vertex2d_bytes(quads, static_cast<uint8_t *>(out), cap);
     return VX_OK;
 }
+
+// The ground of a field as sun points (include/voxmap.h): per column, x fastest,
+// the top face of its topmost block (R == G == 0, as the march sees a block).
+extern "C" int vx_ground_points(const uint8_t *rgba, int X, int Y, int Z, vx_sun_point *points, int32_t *columns,
+                                size_t cap, size_t *n_out) {
+    using namespace vx;
+    if (!rgba || !n_out || X <= 0 || Y <= 0 || Z <= 0 || X > 65535 || Y > 65535)
+        return set_error(VX_EINVAL, "vx_ground_points: bad arguments");
+    const size_t n = (size_t)X * Y;
+    size_t m = 0;
+    for (size_t i = 0; i < n; i++)
+        for (int z = Z - 1; z >= 0; z--) {
+            const uint8_t *t = rgba + 4 * (i + n * (size_t)z);
+            if (t[0] != 0 || t[1] != 0) continue;
+            if (z == Z - 1) break;              // no cell above it in the grid
+            if (points) {
+                if (m >= cap) return set_error(VX_EINVAL, "vx_ground_points: output buffer too small");
+                vx_sun_point &p = points[m];
+                p.cell[0] = (int32_t)(i % (size_t)X); p.cell[1] = (int32_t)(i / (size_t)X); p.cell[2] = z + 1;
+                p.fract[0] = 0.5f; p.fract[1] = 0.5f; p.fract[2] = 0.0f;
+                p.normal_idx = 4;
+                p.reserved = 0;
+                if (columns) columns[m] = (int32_t)i;
+            }
+            m++;
+            break;
+        }
+    *n_out = m;
+    return VX_OK;
+}

@@ -187,6 +187,43 @@ int vx::check_frame(const vx_frame_params *p, int w, int h, int fmt) {
     return VX_OK;
 }
 
+int vx::check_sun_query(const void *points, int n, const float (*suns)[3], int k, uint32_t flags, const void *out,
+                        int on_device) {
+    if (!points || !suns || !out) return set_error(VX_EINVAL, "vx_query_sun: null argument");
+    if (n < 0 || n > VX_MAX_QUERY_RAYS) return set_error(VX_EINVAL, "vx_query_sun: n out of range (0 .. 2^26)");
+    if (k < 1 || k > VX_MAX_SUNS) return set_error(VX_EINVAL, "vx_query_sun: k out of range (1 .. VX_MAX_SUNS)");
+    if (flags & ~VX_SUNQ_NO_EXIT) return set_error(VX_EINVAL, "vx_query_sun: unknown flag bits");
+    for (int j = 0; j < k; j++) {
+        const float *r = suns[j];
+        if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2]))
+            return set_error(VX_EINVAL, "vx_query_sun: non-finite sun direction " + std::to_string(j));
+        if (r[0] == 0.0f && r[1] == 0.0f && r[2] == 0.0f)
+            return set_error(VX_EINVAL, "vx_query_sun: all-zero sun direction " + std::to_string(j));
+    }
+    if (on_device && (((uintptr_t)points & 15u) || ((uintptr_t)out & 3u)))
+        return set_error(VX_EINVAL, "vx_query_sun: device points must be 16-byte aligned, out 4-byte");
+    return VX_OK;
+}
+
+// One sun as k_sun_query reads it.  The fast march paths for a query: every 2^-10
+// <= |r_i| <= 1 -- sun_ray()'s rule (the frames': normalised suns) plus the upper
+// bound its exactness notes assume (vx_march.h march_len_fract: a step moves an
+// axis by at least 2^-10 * 1e-4 "since |r| <= 1"); any other finite direction
+// takes march_literal.  cull: render.frag:228-229 per axis normal -- shadeFactor
+// = u_sunDir.z < 0 ? 0 : sqrt(max(0, dot(n, u_sunDir))), and dot(n, sun) for the
+// normal of index n (render.vert:14-17) is +-sun[n >> 1] (the other products are
+// zeros); the frame marches only where it is > 0 (:232).
+void vx::sun_query_entry(const float r[3], SunQ &q) {
+    std::memset(&q, 0, sizeof q);
+    sun_ray(r, q.S);
+    q.S.fast = q.S.fast && q.S.abs[0] <= 1.0f && q.S.abs[1] <= 1.0f && q.S.abs[2] <= 1.0f;
+    q.sg = (r[0] > 0.0f ? 1 : 0) | (r[1] > 0.0f ? 2 : 0) | (r[2] > 0.0f ? 4 : 0);
+    for (int n = 0; n < 6; n++) {
+        const float along = (n & 1) ? -r[n >> 1] : r[n >> 1];
+        if (r[2] < 0.0f || !(along > 0.0f)) q.cull |= 1 << n;
+    }
+}
+
 
 extern "C" {
 

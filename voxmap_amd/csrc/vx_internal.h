@@ -286,6 +286,43 @@ struct GbufArgs {
 void gbuffer_frame(const vx_frame_params &p, int w, int h, int X, int Y, int Z, int pad, GbufArgs &a);
 int launch_gbuffer(const GbufArgs &a, void *stream);
 
+// One sun of a sun query (vx_sun_query.hip) as the kernel's scalar loads read it:
+// sun_ray()'s constants with `fast` decided by the query's own rule (every 2^-10
+// <= |r_i| <= 1: a query's suns need not be normalised, and march_len_fract's
+// exactness note in vx_march.h assumes |r| <= 1), the axis-sign pattern of the
+// specialised march loops, and the face test of render.frag:228-229 per normal.
+struct SunQ {                // 64 bytes
+    SunRay S;
+    int sg;                  // bit i: r_i > 0 (FrameConsts::sun_sg's meaning)
+    int cull;                // bit n: a point on a face of normal index n fails the face test for this sun
+};
+void sun_query_entry(const float r[3], SunQ &q);   // vx_host.cpp
+// Parameters of one sun-query launch (by value).  k: the scene's KernelArgs
+// (scene_consts) with sunc = nullptr and fc.max_steps = MAX_STEPS -- what the
+// march variants of vx_march.h read; the kernel touches nothing else of it, so
+// only those words are ever loaded from the kernarg segment.
+struct SunQueryArgs {
+    KernelArgs k;
+    const void *points;      // n vx_sun_point, 16-byte aligned
+    uint32_t *out;           // n * words
+    const SunQ *suns;        // nsuns entries on the device
+    unsigned long long *stats;   // SS_COUNT device counters, or nullptr
+    int n, nsuns, words;     // words = VX_SUN_WORDS(nsuns)
+};
+enum SunStatSlot { SS_INVALID = 0, SS_RAYS, SS_CULLED, SS_LIT, SS_FETCH, SS_COUNT };
+int launch_sun_query(const SunQueryArgs &a, void *stream);
+// The sun queries' own march copies: `channels` padded int8 channels (border SB, as launch_sun_pad and
+// launch_sun_exit leave them) copied into a border of SBq >= SB cells of -1.  A query starts a march
+// anywhere, so a step whose axes tie (the literal length of render.frag:105-116, up to sqrt(3) times the
+// one-axis length) can come about on any step; SBq is sized for it (sun_query_border).
+int launch_sun_widen(const int8_t *src, int8_t *dst, int X, int Y, int Z, int SB, int SBq, int channels, void *stream);
+// floor(1.7324 * Z) + 2: a step from f in [0, 1) moves an axis by less than sqrt(3) * 1.0001 * safe *
+// (1 + 2^-20) < 1.7324 * Z cells (safe <= Z), so it lands at most floor(1.7324 * Z) + 1 cells from its cell
+constexpr int sun_query_border(int Z) { return (int)(1.7324 * Z) + 2; }
+// vx_query_sun's checks that need no scene (vx_host.cpp)
+int check_sun_query(const void *points, int n, const float (*suns)[3], int k, uint32_t flags, const void *out,
+                    int on_device);
+
 // Launchers (vx_dispatch.hip).  Return a hipError_t as int.
 int launch_render(const KernelArgs &a, int pixel_format, void *stream);
 // The render kernel's modes: k_render's EXT template argument (vx_render.h), an

@@ -129,6 +129,34 @@ def hits_visible(hits: np.ndarray) -> np.ndarray:
     return ~hidden
 
 
+# ---- sun queries (vx_query_sun): the numpy mirror of vx_sun_point ----
+SUN_POINT_DTYPE = np.dtype([("cell", np.int32, 3), ("fract", np.float32, 3), ("normal_idx", np.int32),
+                            ("reserved", np.uint32)])
+
+
+def ground_points(field_zyx4: np.ndarray):
+    """The ground of a map.bin field (Z, Y, X, 4) as sun points (vx_ground_points, a pure host function):
+    (points[m] SUN_POINT_DTYPE, columns[m] int32 = x + X*y), the top face of each column's topmost block."""
+    f = np.ascontiguousarray(field_zyx4, np.uint8)
+    Z, Y, X, _ = f.shape
+    n = C.c_size_t()
+    check(lib().vx_ground_points(f.ctypes.data, X, Y, Z, None, None, 0, C.byref(n)))
+    pts, cols = np.zeros(n.value, SUN_POINT_DTYPE), np.zeros(n.value, np.int32)
+    if n.value:
+        check(lib().vx_ground_points(f.ctypes.data, X, Y, Z, pts.ctypes.data, cols.ctypes.data, n.value, C.byref(n)))
+    return pts, cols
+
+
+def points_of_hits(hits: np.ndarray) -> np.ndarray:
+    """The first record of each vx_query_rays result with n >= 1 as a sun point, keeping its
+    normal_idx ("is what I clicked in the sun"): SUN_POINT_DTYPE, in the order of those results."""
+    h = np.asarray(hits, dtype=HIT_DTYPE).reshape(-1)
+    s = h["s"][h["n"] >= 1, 0]
+    out = np.zeros(len(s), SUN_POINT_DTYPE)
+    out["cell"], out["fract"], out["normal_idx"] = s["cell"], s["fract"], s["normal_idx"]
+    return out
+
+
 # ---- the frame's planes (vx_render_gbuffer) ----
 GBUFFER_PLANES = ("depth", "opaque_depth", "surface")
 _PLANE_DTYPE = {"depth": np.float32, "opaque_depth": np.float32, "surface": np.uint32}
@@ -347,6 +375,42 @@ class Scene:
         check(lib().vx_query_rays(self.handle, C.c_void_p(rays_ptr), int(n), C.c_void_p(hits_ptr), 1,
                                   C.c_void_p(stream) if stream else None, C.byref(st) if st is not None else None))
         return st
+
+    def query_sun(self, points: np.ndarray, suns, *, max_steps: int = 0, flags: int = 0, stats: bool = False):
+        """Which of the k ``suns`` (k x 3 directions, as u_sunDir) light each of the n ``points``
+        (SUN_POINT_DTYPE, host): an (n, sun_words(k)) uint32 array -- word 0 the number of suns that
+        light the point or SUN_INVALID, then the mask bits -- and the call's SunStats when ``stats``
+        (vx_query_sun)."""
+        p = np.ascontiguousarray(np.asarray(points, dtype=SUN_POINT_DTYPE).reshape(-1))
+        sd = np.ascontiguousarray(np.asarray(suns, dtype=np.float32).reshape(-1, 3))
+        out = np.zeros((p.size, _abi.sun_words(len(sd))), np.uint32)
+        st = _abi.SunStats() if stats else None
+        if p.size:
+            check(lib().vx_query_sun(self.handle, p.ctypes.data, int(p.size), sd.ctypes.data, int(len(sd)),
+                                     int(max_steps), int(flags), out.ctypes.data, 0, None,
+                                     C.byref(st) if st is not None else None))
+        return (out, st) if stats else out
+
+    def query_sun_device(self, points_ptr: int, n: int, suns, out_ptr: int, *, max_steps: int = 0, flags: int = 0,
+                         stream=None, stats: bool = False):
+        """vx_query_sun on device arrays (e.g. torch tensors' data_ptr(); ``suns`` stays a host
+        array): stream-ordered, no synchronisation unless ``stats``."""
+        sd = np.ascontiguousarray(np.asarray(suns, dtype=np.float32).reshape(-1, 3))
+        st = _abi.SunStats() if stats else None
+        check(lib().vx_query_sun(self.handle, C.c_void_p(points_ptr), int(n), sd.ctypes.data, int(len(sd)),
+                                 int(max_steps), int(flags), C.c_void_p(out_ptr), 1,
+                                 C.c_void_p(stream) if stream else None, C.byref(st) if st is not None else None))
+        return st
+
+    def sun_hours(self, hours) -> np.ndarray:
+        """(Y, X) uint16: per column of the scene's own field, how many of ``hours`` (sun_from_hour
+        of each) light its ground point (ground_points); 0 where a column has none."""
+        X, Y, _ = self.dims
+        pts, cols = ground_points(self.read_field())
+        out = np.zeros(X * Y, np.uint16)
+        if len(pts):
+            out[cols] = self.query_sun(pts, [sun_from_hour(h) for h in hours])[:, 0]
+        return out.reshape(Y, X)
 
     def gbuffer(self, frame: Frame, planes=GBUFFER_PLANES, stats: bool = False):
         """The frame's depth and surface planes (vx_render_gbuffer) to host memory: a dict of
