@@ -43,7 +43,10 @@ extern "C" {
  * (vx_render_gbuffer, vx_gbuffer_planes, VX_SURF_*) change no existing signature
  * or layout.
  * Still ABI 10, additive only: the sun queries (vx_query_sun, vx_ground_points
- * and their structs) change no existing signature or layout. */
+ * and their structs) change no existing signature or layout.
+ * Still ABI 10, additive only: orthographic frames (vx_render_ortho,
+ * vx_pixel_ray_ortho, vx_frame_from_ortho) change no existing signature or
+ * layout. */
 #define VX_ABI_VERSION 10
 
 /* error codes */
@@ -629,6 +632,70 @@ typedef struct vx_mgpu_xfer {
  * ncclRecv (rank 0) / ncclSend (the owner) inside one RCCL group. */
 int vx_mgpu_transfers(int w, int h, int band_rows, int pixel_format, int nranks, int rank, vx_mgpu_xfer *out,
                       int cap);
+
+/* --- orthographic frames (DESIGN.md §3 "Orthographic frames") ---------------
+ * Map views: a plan, an oblique "isometric" view, a facade elevation, a section
+ * cut -- parallel rays, a constant scale, tiles that join seamlessly, with the
+ * sun shadows, AO and glass of the perspective frame.  An orthographic frame
+ * reuses vx_frame_params unchanged: the camera (cam_cell + cam_fract) is the
+ * centre of the image plane, ray_fwd the direction every ray shares, ray_right
+ * and ray_up the half extents of the image plane in cells.
+ *
+ * vx_pixel_ray_ortho, a pure host function, is the ray of pixel (px, py): nx, ny
+ * as in vx_pixel_ray; per axis i, in fp32, this order, no contraction:
+ *   a = (nx * right_i) + (ny * up_i);  s = cam_fract_i + a;  fl = floorf(s);
+ *   cell_i = cam_cell_i + (int)fl;  fract_i = fminf(s - fl, 0x1.fffffep-1f)
+ * (s - fl rounds to 1.0f for a tiny negative s; the clamp keeps fract below 1);
+ * dir = ray_fwd, t_max = INFINITY, reserved = 0.  The result is a vx_query_rays
+ * ray as it stands: picking in an orthographic view needs nothing else.  px, py,
+ * w or h out of range, or an origin that is no cell: VX_EINVAL.
+ *
+ * vx_render_ortho: let E(x, y) be p with cam_cell / cam_fract replaced by that
+ * ray's origin and ray_right = ray_up = 0 (ray_fwd unchanged).  Pixel (x, y) of
+ * the frame is the single pixel of vx_render(scene, E(x, y), 1, 1, pixel_format):
+ * in a 1 x 1 frame nx = ny = 0, so its ray is ray_fwd exactly.  That fixes the
+ * quad-relative split, glass in draw order with stacked panes, the canvas blend,
+ * rayDir = normalize(fragment - origin) and the sky's offset from the pixel's own
+ * origin, and the RGBA8 quantisation.  Each vx_stats counter is the sum over the
+ * pixels of that counter of the 1 x 1 frames (the sun exit, cone and doom copies
+ * depend on the sun alone: they are the scene's, shared with vx_render);
+ * shadow_rays_resolved is 0; the wave-iteration diagnostics are the launch's own;
+ * alg_bytes by the formula above; kernel_ms the launches' time; vx_render's
+ * serialisation rule for calls with stats holds.
+ *
+ * ss is 1, 2 or 4.  ss = 1: the frame above, no scratch.  ss > 1: vx_render_aa's
+ * resolve of the orthographic frame H of (ss*w) x (ss*h) pixels of the same p
+ * (the sub-pixel rays are H's pixel rays), H rendered in the chunks
+ * vx_aa_plan_for returns into a stream-ordered intermediate of at most
+ * scratch_cap bytes, each resolved right behind it; stats are H's.  out,
+ * out_on_device, stream, the alignment and the synchronisation are
+ * vx_render_aa's; no caller stream handle is kept.
+ *
+ * VX_EINVAL before any GPU call: a NULL scene, params or out; w, h, ss*w or ss*h
+ * outside 1 .. 32768; a bad ss, scratch_cap or alignment (as vx_render_aa);
+ * quality == 0; a cam_fract outside [0, 1); a non-finite basis component, or
+ * ray_fwd all zero; |cam_cell_i| + ceil(|right_i| + |up_i|) + 2 >= 2^22 on an
+ * axis (every pixel's origin is then a camera vx_render accepts);
+ * shadow_samples > 1; a flag outside the accepted set, which is
+ * VX_FLAG_NO_SHADOW, NO_AO, NO_CLOUDS, PRIMARY_ONLY, REFLECT, ROUGH, UNIT_GBUF,
+ * GLASS_SINGLE, NO_EXIT, NO_CONE and NO_DOOM.  Not supported, and rejected
+ * rather than approximated: soft shadows, VX_FLAG_REFLECT_ALL, GLASS_ORDER,
+ * SOFT_POOL, SOFT_BRICK, INT_INDEX and ROWS_BOTTOM_UP.
+ *
+ * vx_frame_from_ortho, a pure host function in double, rounded to float at the
+ * end: e = (cos el cos az, cos el sin az, sin el) points from the target to the
+ * viewer, ray_fwd = f = -e, r = (-sin az, cos az, 0), u = r x f; ray_right =
+ * half_width * r, ray_up = half_width * h / w * u (square pixels); the camera is
+ * target + back * e, split as vx_frame_from_matrix splits cam_pos; quality = 1;
+ * the other fields are left as they are.  el = pi/2, az = -pi/2 is the north-up
+ * plan (f = -z, r = +x, u = +y).  half_width <= 0, a non-finite input, w or h
+ * < 1: VX_EINVAL. */
+int vx_render_ortho(vx_scene *scene, const vx_frame_params *p, int w, int h, int ss,
+                    int pixel_format, void *out, int out_on_device, void *stream,
+                    size_t scratch_cap, vx_stats *stats);
+int vx_pixel_ray_ortho(const vx_frame_params *p, int w, int h, int px, int py, vx_ray *out);
+int vx_frame_from_ortho(const double target[3], double azimuth, double elevation,
+                        double half_width, double back, int w, int h, vx_frame_params *p);
 
 /* --- host helpers (map.js / math.js / sdf.cpp / utils.js) ----------------- */
 /* map.js:373-391 orbit camera + math.js:37-42 projection (with its sqrt(aspect)

@@ -18,8 +18,10 @@ from .renderer import aa_plan
 from .renderer import GBUFFER_PLANES, SURF_DTYPE, unpack_surface
 from ._abi import MAX_SUNS, SUN_INVALID, SUNQ_NO_EXIT, SunStats, sun_words
 from .renderer import SUN_POINT_DTYPE, ground_points, points_of_hits
+from .renderer import frame_from_ortho, pixel_ray_ortho
 
 __all__ = [
+    "frame_from_ortho", "pixel_ray_ortho",
     "MAX_SUNS", "SUN_INVALID", "SUNQ_NO_EXIT", "SunStats", "sun_words", "SUN_POINT_DTYPE", "ground_points",
     "points_of_hits",
     "Scene", "Frame", "FrameParams", "Stats", "VoxmapError", "lib", "make_frame", "frame_from_orbit",

@@ -229,6 +229,11 @@ SIGNATURES = [
     ("vx_render_aa", C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                C.c_int, C.c_void_p, C.c_size_t, C.POINTER(Stats)]),
     ("vx_aa_plan_for", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(AaPlan)]),
+    ("vx_render_ortho", C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                  C.c_int, C.c_void_p, C.c_size_t, C.POINTER(Stats)]),
+    ("vx_pixel_ray_ortho", C.c_int, [C.POINTER(FrameParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Ray)]),
+    ("vx_frame_from_ortho", C.c_int, [C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                                      C.c_int, C.POINTER(FrameParams)]),
     ("vx_last_error", C.c_char_p, []),
     ("vx_abi_version", C.c_int, []),
 ]

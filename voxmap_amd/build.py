@@ -18,7 +18,7 @@ OUT = os.path.join(HERE, "libvoxmap_hip.so")
 # first: they are the long ones, and the pool starts them first
 SOURCES = ["vx_render_e56.hip", "vx_render_e2.hip", "vx_render_e1.hip", "vx_render_e0.hip", "vx_render_e3.hip",
            "vx_render_e4.hip", "vx_dispatch.hip", "vx_scene_prep.hip", "vx_field_gpu.hip", "vx_query.hip",
-           "vx_gbuffer.hip", "vx_sun_query.hip", "vx_resolve.hip", "vx_api.cpp", "vx_host.cpp", "vx_codec.cpp", "vx_field.cpp", "vx_frame.cpp", "vx_mgpu.cpp"]
+           "vx_gbuffer.hip", "vx_sun_query.hip", "vx_ortho.hip", "vx_resolve.hip", "vx_api.cpp", "vx_host.cpp", "vx_codec.cpp", "vx_field.cpp", "vx_frame.cpp", "vx_mgpu.cpp"]
 # every header under csrc/: an object is rebuilt when any of them is newer (the
 # render kernel's stage headers, vx_math.h .. vx_pixel.h, are included by vx_render.h)
 HEADERS = ["vx_internal.h", "vx_device.h", "vx_math.h", "vx_loads.h", "vx_march.h", "vx_walk.h", "vx_sample.h",

@@ -827,7 +827,115 @@ static int aa_chunks(vx_scene *s, const vx_frame_params *p, int w, int h, int fm
     return VX_OK;
 }
 
+// One k_ortho launch: rows [row0, row0 + rows) of the w x h orthographic frame of p,
+// compact at out_dev.  The frame's part of the arguments as do_render fills it (the
+// sun, the colours, the exit copy through frame_exit, pinned until the launch is
+// enqueued), and what every ray shares (ortho_frame).
+static int do_ortho(vx_scene *s, const vx_frame_params *p, int w, int h, int row0, int rows, int fmt, void *out_dev,
+                    hipStream_t st, vx_stats *stats) {
+    OrthoArgs oa;
+    std::memset(&oa, 0, sizeof oa);
+    KernelArgs &a = oa.k;
+    std::memcpy(&a, &s->ka, sizeof a);
+    if (p->flags & VX_FLAG_NO_EXIT) a.sunx = nullptr;
+    a.quad_gbuf = (p->flags & VX_FLAG_UNIT_GBUF) ? 0 : 1;
+    a.w = w; a.h = h;
+    a.out = out_dev; a.p = *p;
+    a.max_shadow_steps = p->max_shadow_steps > 0 ? p->max_shadow_steps : 2 * s->Z;   // render.frag:12
+    frame_consts(*p, w, h, s->X, s->Y, s->Z, a.max_shadow_steps, a.fc);
+    ortho_frame(*p, oa);
+    oa.row0 = row0; oa.rows = rows;
+    std::unique_lock<std::mutex> cone_lock(s->cone_mu);
+    vx_scene::Cone *cone = nullptr;
+    VX_CHECK(frame_exit(s, p, a.fc, st, &a.sunc, nullptr, nullptr, &cone));
+    if (!cone) cone_lock.unlock();
+    if (stats) {
+        a.stats = s->d_stats.get();
+        VX_CHECK(stats_begin(s, (size_t)ST_COUNT * 64, st));
+    }
+    const int rc = launch_ortho(oa, fmt, st);
+    if (rc) return set_error(VX_EDEVICE, std::string("ortho launch failed: ") + hipGetErrorString((hipError_t)rc));
+    if (cone) cone_lock.unlock();   // enqueued: a recycle now waits for this render
+    if (stats) {
+        unsigned long long v[ST_COUNT];
+        float ms = 0.0f;
+        VX_CHECK(stats_end(s, v, ST_COUNT, st, &ms));
+        fill_stats(stats, v, ms, pixel_bytes(fmt));
+    }
+    return VX_OK;
+}
+
+// vx_render_ortho's chunks, as aa_chunks: chunk c is rows [ss * y0, ss * (y0 + rows)) of the
+// (ss*w) x (ss*h) orthographic frame, rendered compact into `scratch` and resolved right
+// behind it into its rows of the w x h device frame d_out.  stats: the chunks' counters
+// summed, their kernel times plus the resolves'.
+static int ortho_chunks(vx_scene *s, const vx_frame_params *p, int w, int h, int fmt, const vx_aa_plan &plan, void *scratch,
+                        void *d_out, hipStream_t st, vx_stats *stats) {
+    const int ss = plan.ss, W = ss * w, H = ss * h;
+    vx_stats sum;
+    std::memset(&sum, 0, sizeof sum);
+    for (int c = 0; c < plan.n_chunks; c++) {
+        const int y0 = c * plan.chunk_rows_out, rows = std::min(plan.chunk_rows_out, h - y0);
+        vx_stats cs;
+        VX_CHECK(do_ortho(s, p, W, H, ss * y0, ss * rows, fmt, scratch, st, stats ? &cs : nullptr));
+        if (stats) VX_HIP(hipEventRecord(s->ev0.get(), st));
+        const int rc = launch_resolve(scratch, static_cast<char *>(d_out) + (size_t)y0 * w * pixel_bytes(fmt), w, rows, ss,
+                                      W, fmt, st);
+        if (rc) return set_error(VX_EDEVICE, std::string("resolve launch failed: ") + hipGetErrorString((hipError_t)rc));
+        if (stats) {
+            float ms = 0.0f;
+            VX_HIP(hipEventRecord(s->ev1.get(), st));
+            VX_HIP(hipEventSynchronize(s->ev1.get()));
+            VX_HIP(hipEventElapsedTime(&ms, s->ev0.get(), s->ev1.get()));
+            uint64_t *a = &sum.pixels;
+            const uint64_t *b = &cs.pixels;
+            for (size_t i = 0; i < offsetof(vx_stats, kernel_ms) / sizeof(uint64_t); i++) a[i] += b[i];
+            sum.kernel_ms += cs.kernel_ms + (double)ms;
+        }
+    }
+    if (stats) *stats = sum;
+    return VX_OK;
+}
+
 extern "C" {
+
+int vx_render_ortho(vx_scene *s, const vx_frame_params *p, int w, int h, int ss, int fmt, void *out, int out_on_device,
+                    void *stream, size_t scratch_cap, vx_stats *stats) {
+    // every check comes before the first GPU call
+    if (!p || !out) return set_error(VX_EINVAL, "vx_render_ortho: null params or out");
+    vx_aa_plan plan;
+    VX_CHECK(vx_aa_plan_for(w, h, ss, fmt, scratch_cap, &plan));
+    if (!s) return set_error(VX_EINVAL, "vx_render_ortho: null scene");
+    VX_CHECK(check_ortho(p, ss * w, ss * h, fmt));
+    const unsigned need = VX_FLAG_UNIT_GBUF | VX_FLAG_GLASS_SINGLE;
+    if (!s->d_qface && (p->flags & need) != need)
+        return set_error(VX_EINVAL, "this scene has no face table (it did not fit in device memory): its orthographic "
+                                    "frames need VX_FLAG_UNIT_GBUF | VX_FLAG_GLASS_SINGLE");
+    if (out_on_device && ((uintptr_t)out & (fmt == VX_PIXEL_RGBA32F ? 15u : 3u)))
+        return set_error(VX_EINVAL, "vx_render_ortho: a device out must be aligned to 16 bytes (RGBA32F) or 4 (RGBA8)");
+    VX_HIP(hipSetDevice(s->device));
+    hipStream_t st = stream_of(s, stream);
+    const size_t bytes = (size_t)w * h * pixel_bytes(fmt);
+    void *scratch = nullptr, *d_out = out_on_device ? out : nullptr;
+    int rc = VX_OK;
+    hipError_t e = ss > 1 ? hipMallocAsync(&scratch, plan.scratch_bytes, st) : hipSuccess;
+    if (e == hipSuccess && !out_on_device) e = hipMallocAsync(&d_out, bytes, st);
+    if (e != hipSuccess) rc = set_error(VX_EDEVICE, std::string("vx_render_ortho: staging failed: ") + hipGetErrorString(e));
+    if (rc == VX_OK)
+        rc = ss > 1 ? ortho_chunks(s, p, w, h, fmt, plan, scratch, d_out, st, stats)
+                    : do_ortho(s, p, w, h, 0, h, fmt, d_out, st, stats);
+    if (rc == VX_OK && !out_on_device) {
+        e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = set_error(VX_EDEVICE, std::string("vx_render_ortho: readback failed: ") + hipGetErrorString(e));
+    }
+    if (scratch) (void)hipFreeAsync(scratch, st);
+    if (!out_on_device) {
+        if (d_out) (void)hipFreeAsync(d_out, st);
+        (void)hipStreamSynchronize(st);
+    }
+    return rc;
+}
 
 int vx_render_aa(vx_scene *s, const vx_frame_params *p, int w, int h, int ss, int fmt, void *out, int out_on_device,
                  void *stream, size_t scratch_cap, vx_stats *stats) {

@@ -113,6 +113,11 @@ int launch_render(const KernelArgs &a, int fmt, void *stream) {
     return (int)hipGetLastError();
 }
 
+int launch_reduce_stats(unsigned long long *stats, void *stream) {
+    hipLaunchKernelGGL(k_reduce_stats, dim3(1), dim3(64), 0, (hipStream_t)stream, stats);
+    return (int)hipGetLastError();
+}
+
 int launch_detile(const void *tiles, void *frame, int w, int h, int ts, int tiles_x, const int *ids,
                   int n_tiles, int fmt, void *stream) {
     const size_t n = (size_t)ts * ts * n_tiles;

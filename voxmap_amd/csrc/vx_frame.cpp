@@ -206,6 +206,28 @@ void gbuffer_frame(const vx_frame_params &p, int w, int h, int X, int Y, int Z, 
     a.rcp_h = 1.0f / a.fh;
 }
 
+// What every ray of an orthographic frame shares (vx_internal.h OrthoArgs): the
+// direction, its reciprocal as ray_rcp's IEEE branch forms it, primary()'s hp and
+// s, the octant copy, and whether the direction's length is in normalize3_ranged's
+// domain -- rays_ranged's bounds for the one ray fwd (S = |fwd| in [2^-28, 2^40)).
+void ortho_frame(const vx_frame_params &p, OrthoArgs &a) {
+    a.oct = 0;
+    double l2 = 0.0;
+    for (int i = 0; i < 3; i++) {
+        // the 1 x 1 frame's ray (fwd + 0 * right) + 0 * up: fwd, with a -0 component made +0
+        const float d = (p.ray_fwd[i] + 0.0f) + 0.0f;
+        a.d[i] = d;
+        a.iv[i] = d != 0.0f ? 1.0f / d : INFINITY;
+        const bool neg = d < 0.0f;
+        a.hp[i] = neg ? 0.0f : 1.0f;
+        a.sg[i] = neg ? -1.0f : 1.0f;
+        a.oct |= neg ? 1 << i : 0;
+        l2 += (double)d * (double)d;
+    }
+    const double len = std::sqrt(l2);
+    a.ranged = len >= 0x1p-28 && len < 0x1p40 ? 1 : 0;
+}
+
 }  // namespace vx
 
 namespace vx {

@@ -187,6 +187,37 @@ int vx::check_frame(const vx_frame_params *p, int w, int h, int fmt) {
     return VX_OK;
 }
 
+// vx_render_ortho's frame checks: check_frame's, and what makes every pixel's
+// origin a camera vx_render would accept and its 1 x 1 frame one k_ortho shades
+int vx::check_ortho(const vx_frame_params *p, int w, int h, int fmt) {
+    if (const int rc = check_frame(p, w, h, fmt)) return rc;
+    if (p->quality == 0) return set_error(VX_EINVAL, "vx_render_ortho: quality 0 (the 2D mode) has no orthographic frame");
+    if (p->ray_fwd[0] == 0.0f && p->ray_fwd[1] == 0.0f && p->ray_fwd[2] == 0.0f)
+        return set_error(VX_EINVAL, "vx_render_ortho: ray_fwd is zero");
+    // a pixel's origin cell is cam_cell + floor(cam_fract + nx * right + ny * up), |nx|, |ny| < 1
+    for (int i = 0; i < 3; i++) {
+        const double reach = std::ceil(std::fabs((double)p->ray_right[i]) + std::fabs((double)p->ray_up[i]));
+        if (std::fabs((double)p->cam_cell[i]) + reach + 2.0 >= (double)(1 << 22))
+            return set_error(VX_EINVAL, "vx_render_ortho: the image plane leaves |cell| < 2^22 (cam_cell, ray_right, ray_up)");
+    }
+    if (p->shadow_samples > 1) return set_error(VX_EINVAL, "vx_render_ortho: soft shadows (shadow_samples > 1) are not supported");
+    const struct { uint32_t bit; const char *name; } rejected[] = {
+        {VX_FLAG_REFLECT_ALL, "VX_FLAG_REFLECT_ALL"}, {VX_FLAG_GLASS_ORDER, "VX_FLAG_GLASS_ORDER"},
+        {VX_FLAG_SOFT_POOL, "VX_FLAG_SOFT_POOL"}, {VX_FLAG_SOFT_BRICK, "VX_FLAG_SOFT_BRICK"},
+        {VX_FLAG_INT_INDEX, "VX_FLAG_INT_INDEX"}, {VX_FLAG_ROWS_BOTTOM_UP, "VX_FLAG_ROWS_BOTTOM_UP"}};
+    for (const auto &f : rejected)
+        if (p->flags & f.bit) return set_error(VX_EINVAL, std::string("vx_render_ortho: ") + f.name + " is not supported");
+    const uint32_t accepted = VX_FLAG_NO_SHADOW | VX_FLAG_NO_AO | VX_FLAG_NO_CLOUDS | VX_FLAG_PRIMARY_ONLY | VX_FLAG_REFLECT |
+                              VX_FLAG_ROUGH | VX_FLAG_UNIT_GBUF | VX_FLAG_GLASS_SINGLE | VX_FLAG_NO_EXIT | VX_FLAG_NO_CONE |
+                              VX_FLAG_NO_DOOM;
+    if (p->flags & ~accepted) {
+        char bits[32];
+        std::snprintf(bits, sizeof bits, "0x%x", (unsigned)(p->flags & ~accepted));
+        return set_error(VX_EINVAL, std::string("vx_render_ortho: unknown flag bits ") + bits);
+    }
+    return VX_OK;
+}
+
 int vx::check_sun_query(const void *points, int n, const float (*suns)[3], int k, uint32_t flags, const void *out,
                         int on_device) {
     if (!points || !suns || !out) return set_error(VX_EINVAL, "vx_query_sun: null argument");
@@ -354,6 +385,59 @@ int vx_pixel_ray(const vx_frame_params *p, int w, int h, int px, int py, vx_ray 
         out->dir[i] = (p->ray_fwd[i] + nx * p->ray_right[i]) + ny * p->ray_up[i];
     }
     out->t_max = INFINITY;
+    return VX_OK;
+}
+
+// ---- orthographic frames (host halves: no GPU) ------------------------------
+int vx_pixel_ray_ortho(const vx_frame_params *p, int w, int h, int px, int py, vx_ray *out) {
+    if (!p || !out) return set_error(VX_EINVAL, "vx_pixel_ray_ortho: null argument");
+    if (w <= 0 || h <= 0 || w > 32768 || h > 32768 || px < 0 || py < 0 || px >= w || py >= h)
+        return set_error(VX_EINVAL, "vx_pixel_ray_ortho: pixel or frame size out of range");
+    // the header's formula, fp32, this operation order (k_ortho's)
+    const float nx = (float)(2 * px + 1) / (float)w - 1.0f;
+    const float ny = 1.0f - (float)(2 * py + 1) / (float)h;
+    vx_ray r;
+    std::memset(&r, 0, sizeof r);
+    for (int i = 0; i < 3; i++) {
+        const float a = (nx * p->ray_right[i]) + (ny * p->ray_up[i]);
+        const float s = p->cam_fract[i] + a;
+        const float fl = std::floor(s);
+        if (!(std::fabs(fl) < 1073741824.0f) || std::abs((long long)p->cam_cell[i] + (long long)fl) >= (1ll << 31))
+            return set_error(VX_EINVAL, "vx_pixel_ray_ortho: the pixel's origin is not a cell (non-finite or out of range)");
+        r.cell[i] = p->cam_cell[i] + (int)fl;
+        r.fract[i] = std::fmin(s - fl, 0x1.fffffep-1f);   // s - fl rounds to 1 for a tiny negative s
+        r.dir[i] = p->ray_fwd[i];
+    }
+    r.t_max = INFINITY;
+    *out = r;
+    return VX_OK;
+}
+
+int vx_frame_from_ortho(const double target[3], double azimuth, double elevation, double half_width, double back,
+                        int w, int h, vx_frame_params *p) {
+    if (!target || !p) return set_error(VX_EINVAL, "vx_frame_from_ortho: null argument");
+    if (w < 1 || h < 1) return set_error(VX_EINVAL, "vx_frame_from_ortho: w and h must be >= 1");
+    if (!std::isfinite(target[0]) || !std::isfinite(target[1]) || !std::isfinite(target[2]) || !std::isfinite(azimuth) ||
+        !std::isfinite(elevation) || !std::isfinite(half_width) || !std::isfinite(back))
+        return set_error(VX_EINVAL, "vx_frame_from_ortho: non-finite argument");
+    if (!(half_width > 0.0)) return set_error(VX_EINVAL, "vx_frame_from_ortho: half_width must be > 0");
+    const double ce = std::cos(elevation), se = std::sin(elevation), ca = std::cos(azimuth), sa = std::sin(azimuth);
+    const double e[3] = {ce * ca, ce * sa, se};           // from the target towards the viewer
+    const double f[3] = {-e[0], -e[1], -e[2]};
+    const double r[3] = {-sa, ca, 0.0};
+    const double u[3] = {r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0]};   // r x f
+    const double hh = half_width * (double)h / (double)w;  // square pixels
+    double pos[3];
+    for (int i = 0; i < 3; i++) {
+        p->ray_fwd[i] = (float)f[i];
+        p->ray_right[i] = (float)(half_width * r[i]);
+        p->ray_up[i] = (float)(hh * u[i]);
+        pos[i] = target[i] + back * e[i];
+        if (!(std::fabs(pos[i]) < 2147483000.0))
+            return set_error(VX_EINVAL, "vx_frame_from_ortho: the camera is out of the cell range");
+    }
+    set_cam(pos, p);
+    p->quality = 1;
     return VX_OK;
 }
 

@@ -323,8 +323,31 @@ constexpr int sun_query_border(int Z) { return (int)(1.7324 * Z) + 2; }
 int check_sun_query(const void *points, int n, const float (*suns)[3], int k, uint32_t flags, const void *out,
                     int on_device);
 
+// Parameters of one orthographic launch (vx_ortho.hip; by value).  k: the scene's
+// KernelArgs (scene_consts) with the frame's part as do_render fills it for the same
+// vx_frame_params at the full frame's size -- the sun, the colours, the flags, the
+// exit copy, and the image plane (fc.cam_cell, cam_fract, right, up, fw, fh, rcp_w,
+// rcp_h) the kernel derives each pixel's origin from; the camera-only fields
+// (slabs, kcam, the fp32 index terms) are not read.  The rest is what every ray of
+// the frame shares, from ortho_frame with the fp32 operations the walks perform.
+struct OrthoArgs {
+    KernelArgs k;
+    float d[3];              // ray_fwd: every pixel's direction
+    float iv[3];             // RN(1/d), +inf for d = 0 (a positive axis, as -0 is)
+    float hp[3], sg[3];      // per axis 1 and +1 (d >= 0 or -0) or 0 and -1 (d < 0): primary()'s hp and s
+    int oct;                 // the octant copy the frame walks (bit i: d_i < 0)
+    int ranged;              // 1: |d| in [2^-40, 2^41), normalize3_ranged's domain (the sky's direction)
+    int row0, rows;          // the launch renders rows [row0, row0 + rows) of the k.w x k.h frame, compact at k.out
+};
+void ortho_frame(const vx_frame_params &p, OrthoArgs &a);                   // vx_frame.cpp
+// vx_render_ortho's checks of the frame that need no scene (vx_host.cpp)
+int check_ortho(const vx_frame_params *p, int w, int h, int fmt);
+int launch_ortho(const OrthoArgs &a, int pixel_format, void *stream);       // vx_ortho.hip
+
 // Launchers (vx_dispatch.hip).  Return a hipError_t as int.
 int launch_render(const KernelArgs &a, int pixel_format, void *stream);
+// the 64 slot rows of a STATS launch (flush_counters) summed into the first
+int launch_reduce_stats(unsigned long long *stats, void *stream);
 // The render kernel's modes: k_render's EXT template argument (vx_render.h), an
 // int, so the digit stands in every instantiation's mangled name (ILi<digit>E:
 // kernel_meta.render_params and the recorded profiles read it there).

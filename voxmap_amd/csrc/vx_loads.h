@@ -54,6 +54,16 @@ struct Counters {
     unsigned shadow_resolved;                // shadow rays resolved by the first-step table test (not marched)
 };
 
+// A ray's own origin, for a kernel whose pixels do not share the frame's camera
+// (k_ortho): what FrameConsts::cam_cell, cam_fract and skyOff are to k_render.
+// The helpers that read the camera take one as an optional last argument; the
+// frame kernels pass none, and their code is what it was without it.
+struct RayOrigin {
+    int cc0, cc1, cc2;       // the origin's cell (|cell| < 2^22)
+    float o0, o1, o2;        // and fraction, in [0, 1)
+    float sky0, sky1;        // 1e-4 * (cell.xy + fract.xy) (render.frag:191)
+};
+
 // (float)((t >> 8k) & 0xff) as one v_cvt_f32_ubyteK (left to itself the
 // compiler may fold the mask away and emit a shift + convert)
 __device__ __forceinline__ float cvt_f32_ubyte0(uint32_t t) {

@@ -149,8 +149,9 @@ __device__ __forceinline__ void sky_clear(const FrameConsts &F, float d0, float 
 // ranged: wave-uniform (FrameConsts::rays_ranged for a view ray, false for any
 // other direction) -- one scalar branch, no per-wave test of the lengths
 // (a per-wave guard costs what it saves)
+// org: the ray's own origin (k_ortho), whose sky offset stands in for the frame's
 __device__ __forceinline__ void shade_sky(const KernelArgs &a, float d0, float d1, float d2, float o[4],
-                          Counters &cnt, bool ranged = false) {
+                          Counters &cnt, bool ranged = false, const RayOrigin *org = nullptr) {
     const FrameConsts &F = a.fc;
     const float sunCol[3] = {1.4f, 1.0f, 0.5f};
     float r0, r1, r2;
@@ -194,8 +195,8 @@ __device__ __forceinline__ void shade_sky(const KernelArgs &a, float d0, float d
         for (int i = 0; i < 3; i++) sky[i] = gmix(sky[i], sky[i] * mt[i], w);
     } else {
         sx = sx * (3.0f + n0); sy = sy * (3.0f + n1);
-        sx = sx + F.skyOff[0];
-        sy = sy + F.skyOff[1];
+        sx = sx + (org ? org->sky0 : F.skyOff[0]);
+        sy = sy + (org ? org->sky1 : F.skyOff[1]);
         const float cloudFactor = vexp2(6.0f * (fbm(a, sx + 2.0f * ct, sy + -9.0f * ct) - 1.0f));
         const float scf = sqrtf(cloudFactor);
 #pragma unroll

@@ -161,9 +161,10 @@ __device__ __forceinline__ void shade_block(const KernelArgs &a, const Surf &g, 
 // ext REFLECT: colour seen along the mirror reflection at glass record gl
 // (rd = the camera rayDir at the fragment; R = rd with the face-axis
 // component negated = reflect(rd, n) exactly), oracle reflect_color().
+// org: the view ray's own origin (k_ortho): the mirror ray's sky takes its offset.
 template <int EXT>
 __device__ __forceinline__ void reflect_color(const KernelArgs &a, const Surf &gl, const float rd[3], float out[3],
-                              Counters &cnt) {
+                              Counters &cnt, const RayOrigin *org = nullptr) {
     const int ax = gl.nidx >> 1;
     const float R0 = ax == 0 ? -rd[0] : rd[0], R1 = ax == 1 ? -rd[1] : rd[1], R2 = ax == 2 ? -rd[2] : rd[2];
     const float fl0 = floorf(gl.f0), fl1 = floorf(gl.f1), fl2 = floorf(gl.f2);
@@ -182,8 +183,15 @@ __device__ __forceinline__ void reflect_color(const KernelArgs &a, const Surf &g
     if (walk_reflect(a, B0, B1, B2, o0, o1, o2, R0, R1, R2, s0, s1, s2, h, cnt))
         shade_block<EXT>(a, h, rgba, cnt, true, R0, R1, R2);
     else
-        shade_sky(a, R0, R1, R2, rgba, cnt);
+        shade_sky(a, R0, R1, R2, rgba, cnt, false, org);
     out[0] = rgba[0]; out[1] = rgba[1]; out[2] = rgba[2];
+}
+
+// rayDir of fragment g seen from origin L (render.frag:154), as shade_block forms
+// it from the frame's camera: exact cell differences, one normalize3
+__device__ __forceinline__ void origin_ray(const RayOrigin &L, const Surf &g, float &r0, float &r1, float &r2) {
+    normalize3((g.c0 - (float)L.cc0) + (g.f0 - L.o0), (g.c1 - (float)L.cc1) + (g.f1 - L.o1),
+               (g.c2 - (float)L.cc2) + (g.f2 - L.o2), r0, r1, r2);
 }
 
 // Glass in draw order (render.js:82-91; DESIGN.md §5 "Glass"): the reference
@@ -198,22 +206,29 @@ __device__ __forceinline__ void reflect_color(const KernelArgs &a, const Surf &g
 // then blends P1 (g[0]) over it.  It runs for pixels whose ray crosses two or
 // more panes in front of its surface (primary()'s multi): with one pane dst' =
 // dst.
+// org: the ray's own origin (k_ortho, XE != 0) in the camera's place: the scan
+// walks from it, and each pane's rayDir is taken from it.
 template <int XE>
 __device__ __forceinline__ void glass_chain(const KernelArgs &a, float d0, float d1, float d2, float dst[4], float depth,
-                                            Counters &cnt) {
+                                            Counters &cnt, const RayOrigin *org = nullptr) {
     const FrameConsts &F = a.fc;
     unsigned long long klast = 0;
     bool have_last = false, nearest = false;
     Surf cur;
     float tc;
     unsigned long long kc;
-    while (glass_scan(a, d0, d1, d2, have_last, klast, depth, cur, tc, kc, nearest) && !nearest) {
+    while (glass_scan(a, d0, d1, d2, have_last, klast, depth, cur, tc, kc, nearest, org) && !nearest) {
         depth = tc; klast = kc; have_last = true;
         float src[4], rd[3];
-        shade_block<XE>(a, cur, src, cnt, false, 0.0f, 0.0f, 0.0f, rd);
+        if (org) {
+            origin_ray(*org, cur, rd[0], rd[1], rd[2]);
+            shade_block<XE>(a, cur, src, cnt, true, rd[0], rd[1], rd[2]);
+        } else {
+            shade_block<XE>(a, cur, src, cnt, false, 0.0f, 0.0f, 0.0f, rd);
+        }
         if (XE && (F.flags & (VX_FLAG_REFLECT | VX_FLAG_REFLECT_ALL))) {   // ext REFLECT: panes mirror
             float refl[3];
-            reflect_color<XE>(a, cur, rd, refl, cnt);
+            reflect_color<XE>(a, cur, rd, refl, cnt, org);
             const int ax = cur.nidx >> 1;
             const float cs = gmin(fabsf(ax == 0 ? rd[0] : (ax == 1 ? rd[1] : rd[2])), 1.0f);
             const float x = 1.0f - cs, x2 = x * x;

@@ -468,16 +468,27 @@ __device__ __forceinline__ unsigned long long face_key(const KernelArgs &a, int 
 // and are not counted again.
 __device__ __forceinline__ bool glass_scan(const KernelArgs &a, float d0, float d1, float d2, bool have_last,
                                            unsigned long long klast, float tmax, Surf &h, float &t_out,
-                                           unsigned long long &k_out, bool &nearest) {
+                                           unsigned long long &k_out, bool &nearest,
+                                           const RayOrigin *org = nullptr) {
     const FrameConsts &F = a.fc;
-    const float o0 = F.cam_fract[0], o1 = F.cam_fract[1], o2 = F.cam_fract[2];
-    const int cc0 = F.cam_cell[0], cc1 = F.cam_cell[1], cc2 = F.cam_cell[2];
+    // org: the ray's own origin (k_ortho) in the camera's place, its slabs by frame_consts' expressions
+    const float o0 = org ? org->o0 : F.cam_fract[0], o1 = org ? org->o1 : F.cam_fract[1],
+                o2 = org ? org->o2 : F.cam_fract[2];
+    const int cc0 = org ? org->cc0 : F.cam_cell[0], cc1 = org ? org->cc1 : F.cam_cell[1],
+              cc2 = org ? org->cc2 : F.cam_cell[2];
     const float iv0 = d0 != 0.0f ? 1.0f / d0 : 0.0f, iv1 = d1 != 0.0f ? 1.0f / d1 : 0.0f,
                 iv2 = d2 != 0.0f ? 1.0f / d2 : 0.0f;
     float tlo = 0.0f, thi = kInf;
     bool miss = false;
+    // (the origin's slab bounds in a lambda of their own, called only where org is given: written into
+    // slab's body they changed every frame kernel's code, tools/isa_diff.py)
+    auto org_slab = [&](int i, int edge) {
+        const int cc = i == 0 ? cc0 : (i == 1 ? cc1 : cc2);
+        return (float)(edge - cc) - (i == 0 ? o0 : (i == 1 ? o1 : o2));
+    };
     auto slab = [&](float d, float iv, int i) {
-        const float lo = F.slab_lo[i], hi = F.slab_hi[i];
+        const float lo = org ? org_slab(i, 0) : F.slab_lo[i],
+                    hi = org ? org_slab(i, i == 0 ? a.X : (i == 1 ? a.Y : a.Z)) : F.slab_hi[i];
         if (d != 0.0f) {
             float t0 = lo * iv, t1 = hi * iv;
             if (t0 > t1) { const float tt = t0; t0 = t1; t1 = tt; }

@@ -109,6 +109,32 @@ def pixel_ray(frame: "Frame", px: int, py: int) -> np.ndarray:
     return out[0]
 
 
+def frame_from_ortho(target, azimuth: float, elevation: float, half_width: float, back: float, w: int, h: int, *,
+                     sun=None, hour=1.0, time=123.0, flags=0, max_shadow_steps=0) -> Frame:
+    """An orthographic frame looking at ``target`` from azimuth / elevation (radians), ``half_width`` cells from
+    the centre to the left and right edges, the image plane ``back`` cells from the target
+    (vx_frame_from_ortho); elevation pi/2 with azimuth -pi/2 is the north-up plan.  For Scene.render_ortho."""
+    p = FrameParams()
+    check(lib().vx_frame_from_ortho((C.c_double * 3)(*target), float(azimuth), float(elevation), float(half_width),
+                                    float(back), int(w), int(h), C.byref(p)))
+    sd = sun if sun is not None else sun_from_hour(hour)
+    for i in range(3):
+        p.sun_dir[i] = float(sd[i])
+    p.time = float(time) % 1000.0
+    p.flags = int(flags)
+    p.max_shadow_steps = int(max_shadow_steps)
+    return Frame(p, int(w), int(h))
+
+
+def pixel_ray_ortho(frame: "Frame", px: int, py: int) -> np.ndarray:
+    """The ray of pixel (px, py) of the orthographic ``frame`` as one RAY_DTYPE record (vx_pixel_ray_ortho):
+    its own origin on the image plane, the frame's one direction."""
+    out = np.zeros(1, RAY_DTYPE)
+    check(lib().vx_pixel_ray_ortho(C.byref(frame.params), frame.width, frame.height, int(px), int(py),
+                                   C.cast(out.ctypes.data, C.POINTER(_abi.Ray))))
+    return out[0]
+
+
 def place_rays(u_matrix, cam_pos, places):
     """drawOverlay's projection of ``places`` (n x 3, map.js:117-137) and the rays camera ->
     place with t_max = 1 (vx_place_rays): (views[n] PLACE_VIEW_DTYPE, rays[n] RAY_DTYPE)."""
@@ -318,6 +344,28 @@ class Scene:
         check(lib().vx_render_aa(self.handle, C.byref(frame.params), frame.width, frame.height, int(supersample),
                                  pixel_format, C.c_void_p(out_ptr), 1, C.c_void_p(stream) if stream else None,
                                  int(scratch_cap), C.byref(st) if st is not None else None))
+        return st
+
+    def render_ortho(self, frame: Frame, supersample: int = 1, *, pixel_format=_abi.PIXEL_RGBA32F, stats: bool = False,
+                     scratch_cap: int = 0):
+        """``frame`` as an orthographic frame (vx_render_ortho): the camera is the centre of the image plane,
+        ray_fwd every ray's direction, ray_right / ray_up the plane's half extents in cells; returns
+        (image[h, w, 4], Stats or None).  supersample 2 or 4: resolved on the device as render_aa's."""
+        w, h = frame.width, frame.height
+        out = np.empty((h, w, 4), np.float32 if pixel_format == _abi.PIXEL_RGBA32F else np.uint8)
+        st = Stats() if stats else None
+        check(lib().vx_render_ortho(self.handle, C.byref(frame.params), w, h, int(supersample), pixel_format,
+                                    out.ctypes.data, 0, None, int(scratch_cap), C.byref(st) if st is not None else None))
+        return out, st
+
+    def render_ortho_device(self, frame: Frame, out_ptr: int, supersample: int = 1, *,
+                            pixel_format=_abi.PIXEL_RGBA32F, stats: bool = False, scratch_cap: int = 0, stream=None):
+        """render_ortho into a device buffer of w * h pixels (e.g. a torch tensor's data_ptr());
+        stream-ordered, no synchronisation unless ``stats``."""
+        st = Stats() if stats else None
+        check(lib().vx_render_ortho(self.handle, C.byref(frame.params), frame.width, frame.height, int(supersample),
+                                    pixel_format, C.c_void_p(out_ptr), 1, C.c_void_p(stream) if stream else None,
+                                    int(scratch_cap), C.byref(st) if st is not None else None))
         return st
 
     def render_tiles(self, frame: Frame, tile_size: int, tile_ids, out_ptr: int, *,
