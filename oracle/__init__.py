@@ -4,9 +4,13 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import
 this package, and only as the checker / the timed CPU baseline.  The product
 path (voxmap_amd, libvoxmap_hip.so) never touches it.
 
-Parity status: "parity unpinned" against reference outputs (the reference is
-browser GLSL with no tests or golden images); the oracle is
-pinned by hand-derived known-answer tests (tests/test_oracle_kat.py).
+Parity status: march() and main() of render.frag, and sdf.cpp's map.bin,
+vertex.bin and vertex2d.bin, are pinned word for word and byte for byte to the
+reference's own shader and generator, compiled (oracle/refpin.py; recorded in
+tests/golden/ref_*; tests/test_ref_frag.py, test_ref_sdf.py, test_ref_gpu.py).
+Primary visibility, the blend stage, MSAA, mip sampling and the extensions have
+no reference program to be held to; they rest on the hand-derived known-answer
+tests (tests/test_oracle_kat.py) and the mesh cross-check.
 """
 from __future__ import annotations
 
@@ -53,6 +57,8 @@ _lib = None
 
 def build() -> str:
     subprocess.run(["make", "-s", "-C", _HERE], check=True)
+    from . import refpin
+    refpin.build_maps()        # where make built the reference's generator: its outputs for the pinned maps
     return LIB_PATH
 
 

@@ -6,11 +6,11 @@
  * and bench.py's cpu_baseline leg may load it, and only as the checker or the
  * timed CPU baseline — never as part of the product path.
  *
- * PARITY STATUS: "parity unpinned" against reference outputs.  The reference
- * is GLSL ES 3.00 running in a browser and has no tests, golden images or
- * known-answer vectors; compiling/running the reference's
- * C++ was refused by the environment, so it is read as text
- * only.  The oracle is pinned instead by hand-derived known-answer tests
+ * PARITY STATUS: march() and main() are pinned word for word to the reference's
+ * own render.frag compiled as C++, and the field and mesh to its own sdf.cpp
+ * (oracle/refpin.py, oracle/ref/; recorded under tests/golden/ref_*; DESIGN.md
+ * §4).  Primary visibility, the blend stage and the extensions have no reference
+ * program behind them: they are pinned by hand-derived known-answer tests
  * (tests/test_oracle_kat.py: empty map, single block shadow footprint,
  * closed-form sky, march() traces) and by the plaintext reference assets
  * (res/noise.bin.gz checksums).

@@ -1,6 +1,7 @@
 /*
  * vxo_render.c — CPU ORACLE (test infrastructure only; see vxo.h header).
- * "parity unpinned" against reference outputs (none exist); pinned by the
+ * march() and main() are held word for word to the reference's own shader,
+ * compiled (oracle/refpin.py, tests/test_ref_frag.py); the rest is pinned by the
  * hand-derived KATs in tests/test_oracle_kat.py.
  *
  * Scalar restatement of /root/reference/src/shaders/render.frag (+ render.h,

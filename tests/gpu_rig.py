@@ -109,6 +109,24 @@ def assert_bytes_equal(img, ref):
     _raise_if(img != ref, "bytes")
 
 
+def assert_ints_equal(got, ref, what="values"):
+    """Two integer arrays of one shape and dtype (cells, steps, mask words, quad tables), every element."""
+    got, ref = np.asarray(got), np.asarray(ref)
+    if got.shape != ref.shape or got.dtype != ref.dtype or got.dtype.kind not in "iub":
+        raise AssertionError(f"{what}: {got.dtype} {got.shape} against {ref.dtype} {ref.shape}: not two integer arrays of one kind")
+    _raise_if(got != ref, what)
+
+
+def assert_blob_equal(got, ref, what="blob"):
+    """Two byte strings (a file against its recorded copy): the length, then every byte."""
+    got, ref = bytes(got), bytes(ref)
+    if len(got) != len(ref):
+        raise AssertionError(f"{what}: {len(got)} bytes against {len(ref)}")
+    if got != ref:
+        a, b = np.frombuffer(got, np.uint8), np.frombuffer(ref, np.uint8)
+        _raise_if(a != b, f"{what} bytes")
+
+
 def _dict(st):
     return st if isinstance(st, dict) else st.as_dict()
 

@@ -126,6 +126,67 @@ def s_glass(seed: int = 1, dims=(1024, 256, 32), n_houses: int = 60, n_facades: 
     return g
 
 
+def ref_boxes(seed: int = 7, dims=(1024, 256, 32), n_boxes: int = 40) -> np.ndarray:
+    """Pinned map `boxes`: 40 seeded random boxes in empty space, no ground (so marches leave through
+    z = 0 too), at the generator's fixed size; every colour 1..20 and glass occurs."""
+    X, Y, Z = dims
+    rng = np.random.default_rng(seed)
+    g = np.zeros((Z, Y, X), np.uint8)
+    for k in range(n_boxes):
+        w, d, h = int(rng.integers(3, 40)), int(rng.integers(3, 40)), int(rng.integers(1, 20))
+        x0, y0, z0 = int(rng.integers(0, X - w)), int(rng.integers(0, Y - d)), int(rng.integers(0, Z - h))
+        g[z0:z0 + h, y0:y0 + d, x0:x0 + w] = 1 + k % 21
+    return g
+
+
+def ref_edges(dims=(1024, 256, 32)):
+    """Pinned map `edges`: what a random map does not reach in the generator (sdf.cpp).  Returns (grid,
+    overwrites); overwrites lists (x, y, z, colour) lines a map.txt carries before the grid's own line for
+    that cell (the last write wins, the palette keeps the overwritten colour), each under a taller block of
+    its column or at z = 0, where the 2D rule (sdf.cpp:201) does not see it.
+
+    - the 8 corners of the grid hold blocks; the low one is a 3-cube around an air shaft at cell (0, 0, .),
+      which is the one cell where the field's gradient rule is off (x + y + z > 0, sdf.cpp:440);
+    - full columns on the faces x = 0, x = X - 1, y = 0, y = Y - 1;
+    - a slab in the top layer with air under it, a block in layer 0 only (a column whose top block is at
+      z = 0), single voxels in the bottom, a middle and the top layer;
+    - faces lying on chunk planes (x = 64, y = 32) from either side in one colour, and boxes across them;
+    - a floorless hollow box: inside, the downward radius is cut by max = z (sdf.cpp:437);
+    - glass panes, two of them parallel."""
+    X, Y, Z = dims
+    g = np.zeros((Z, Y, X), np.uint8)
+    for k, (cx, cy, cz) in enumerate((a, b, c) for c in (0, 1) for b in (0, 1) for a in (0, 1)):
+        xs = slice(X - 2, X) if cx else slice(0, 2)
+        ys = slice(Y - 2, Y) if cy else slice(0, 2)
+        zs = slice(Z - 2, Z) if cz else slice(0, 2)
+        g[zs, ys, xs] = 1 + k
+    g[0:3, 0:3, 0:3] = 1
+    g[0:3, 0, 0] = 0                               # the air shaft in the low corner
+    g[:, 100, 0] = 9
+    g[:, 150, X - 1] = 10
+    g[:, 0, 300] = 11
+    g[:, Y - 1, 700] = 12
+    g[Z - 1, 40:80, 200:260] = 13                  # a slab in the top layer, air under it
+    g[0, 120:124, 500:504] = 14                    # a block in layer 0 only
+    g[0, 10, 900] = 15                             # single voxels
+    g[5, 200, 600] = 16
+    g[Z - 1, 128, 512] = 17
+    g[1:6, 40:50, 58:64] = 5                       # +x face on the chunk plane x = 64
+    g[1:6, 52:60, 64:70] = 5                       # -x face on it, the same colour
+    g[1:5, 26:32, 100:110] = 6                     # +y face on the chunk plane y = 32
+    g[1:5, 32:38, 112:120] = 6                     # -y face on it
+    g[1:4, 60:68, 90:100] = 7                      # across y = 64
+    g[2:9, 140:150, 120:136] = 18                  # across x = 128
+    g[0:12, 180:220, 300:340] = 19                 # a hollow box without a floor
+    g[0:11, 181:219, 301:339] = 0
+    g[1:10, 90, 400:420] = GLASS                   # two parallel panes
+    g[1:10, 94, 400:420] = GLASS
+    g[2:8, 100:115, 450] = GLASS
+    g[0:20, 230:234, 800:804] = 20                 # a tall block: the overwritten cells lie under its top
+    overwrites = [(800, 230, 3, 4), (801, 231, 7, GLASS), (500, 120, 0, 2), (0, 100, 0, 16)]
+    return g, overwrites
+
+
 def single_block(dims=(64, 32, 16), at=(20, 12, 1), color=5) -> np.ndarray:
     X, Y, Z = dims
     g = np.zeros((Z, Y, X), np.uint8)
